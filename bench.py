@@ -22,8 +22,16 @@ Workloads (BASELINE.json configs):
 
 Cold inputs: the timed steps rotate over enough input/output buffer sets that
 one rotation touches more than the 256 MiB Infinity Cache, so every step reads
-its samples from HBM (MI355X_MICROARCH.md, Infinity Cache residency rule).  A
-warm replay of one buffer set is reported beside it under "warm".
+its samples from HBM (MI355X_MICROARCH.md, Infinity Cache residency rule).
+
+A plain run sets up, warms up, times the --steps steps and prints the result
+line (value, ms_per_step, the roofline fraction of those same steps).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs; the same arguments give the same files).  --full runs, after
+that, everything measured or checked beside the headline figure: the per-launch
+spread, a warm replay of one buffer set ("warm"), the cfg4 scaling reference,
+the bit-exact check of every buffer set against tests/golden, the gather
+(N > 1) and the CPU baseline.
 
 Prints ONE JSON line on rank 0.  Diagnostics go to stderr.
 """
@@ -405,6 +413,48 @@ def per_launch_us(torch, stream, step, bsets, n):
                      "(diagnostic: the spread of single launches, not part of value)")
 
 
+def frame_sizes(api, wl, bs):
+    """The sizes a step left in buffer set bs (one entry for a payload-only
+    stream), as uint32; a frame that ended in an error raises."""
+    sz = bs.sizes[:1 if wl.get("stream") else bs.sizes.numel()].cpu().numpy().astype(np.uint32)
+    errs = [api.error_name(int(s)) for s in sz if api.is_error(int(s))]
+    if errs:
+        raise RuntimeError(f"frame errors: {errs[:4]}")
+    return sz
+
+
+DUMP_MAX_BYTES = 8 << 20  # frame bytes written as float32: 32 MiB of the 64 MB a dump may take
+DUMP_SEED = 0xA1A5
+
+
+def dump_outputs(out_dir, wl, bs, sz, rank, world):
+    """--dump-outputs: what the caller of the last timed step received in
+    buffer set bs, as float .npy files (every value is an integer, exact in
+    its format):
+      frame_sizes   float64 [frames]     compressed size of every frame (B)
+      frame_sums    float64 [frames]     sum of each frame's bytes (covers all of them)
+      frame_bytes   float32 [<= 8 Mi]    the frames' bytes back to back in frame order
+                                         (the dst_stride padding left out), or a fixed
+                                         seeded sample of them in stream order where
+                                         they are more than DUMP_MAX_BYTES
+    The inputs are synthetic and seeded and the identifiers come from the
+    library's counter, so the same arguments give the same files."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = bs.dst.cpu().numpy()
+    stride = 0 if wl.get("stream") else bs.dstride
+    frames = [host[j * stride:j * stride + int(s)] for j, s in enumerate(sz)]
+    sums = np.array([f.sum(dtype=np.uint64) for f in frames], dtype=np.float64)
+    packed = np.concatenate(frames)
+    limit = max(1, DUMP_MAX_BYTES // world)
+    if packed.size > limit:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, packed.size, limit))
+        packed = packed[idx]
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, a in (("frame_sizes", sz.astype(np.float64)), ("frame_sums", sums),
+                    ("frame_bytes", packed.astype(np.float32))):
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), a)
+
+
 def make_sets(torch, pkg, lib, eng, wl, fids, rotate):
     """The buffer sets the timed steps rotate over: enough that one rotation
     touches more than the Infinity Cache (cold reads)."""
@@ -443,12 +493,20 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None)
     ap.add_argument("--rotate", type=int, default=0,
                     help="buffer sets to rotate over (0: enough to exceed the 256 MiB Infinity Cache)")
-    ap.add_argument("--no-warm", action="store_true", help="skip the warm (one buffer set) replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gather", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the per-launch "
+                         "spread, the warm replay, the scaling reference, the bit-exact check against the golden "
+                         "digests, the gather (N > 1) and the CPU baseline")
+    ap.add_argument("--no-warm", action="store_true", help="with --full: skip the warm (one buffer set) replay")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-gather", action="store_true", help="with --full at N > 1: skip the gather")
     ap.add_argument("--scaling-reference", action="store_true",
-                    help="with --workload at N = 1: also time cfg4 (the per-GPU work of the N > 1 runs)")
+                    help="with --full and --workload at N = 1: also time cfg4 (the per-GPU work of the N > 1 runs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -509,11 +567,20 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     wall_max = float(t.item())
+    # what the last timed step left behind: its frame sizes (an error in one
+    # of them fails the run) and, on request, the frames themselves
+    last = sets[(args.steps - 1) % len(sets)]
+    last_sizes = frame_sizes(api, wl, last)
+    comp_bytes = int(last_sizes.astype(np.uint64).sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl, last, last_sizes, rank, world)
+
+    # ---- everything below the dump runs with --full only ------------------
     launch_us = None
-    if world == 1:
+    if args.full and world == 1:
         launch_us = per_launch_us(torch, stream, step, sets, 20)
     warm = None
-    if not args.no_warm and world == 1:
+    if args.full and not args.no_warm and world == 1:
         wwall, wkern = timed(sets[:1], args.steps, 2)
         warm = dict(value=round(nf * sb * n * args.steps / wwall / 1e9, 3), ms_per_step=round(wwall / args.steps * 1e3, 5),
                     avg_step_gpu_ms=round(wkern, 5),
@@ -521,7 +588,9 @@ def main():
 
     # ---- the single-GPU reference of the scaling runs (not in `value`) -----
     scaling_ref = None
-    if world == 1 and wname != "cfg4" and (args.workload is None or args.scaling_reference):
+    if not args.full:
+        pass
+    elif world == 1 and wname != "cfg4" and (args.workload is None or args.scaling_reference):
         scaling_ref = scaling_reference_n1(torch, pkg, lib, eng, stream, args.steps, args.warmup)
     elif world > 1:
         # rank 0 replays its own shard alone (the other ranks wait): the same
@@ -550,8 +619,7 @@ def main():
     else:
         want = None
     bitexact = None
-    comp_bytes = 0
-    for bs in sets:
+    for bs in (sets if args.full else ()):
         if wl.get("stream"):
             sz0 = int(bs.sizes[:1].cpu().numpy().astype(np.uint32)[0])
             if api.is_error(sz0):
@@ -578,7 +646,7 @@ def main():
 
     # ---- gather of compressed frames to rank 0 (not in `value`) -----------
     gather = None
-    if world > 1 and not args.no_gather:
+    if args.full and world > 1 and not args.no_gather:
         bs = sets[0]
         # identifiers of one process over the node's frames with the default
         # counter (first draw 0): one context per stream, initialised in
@@ -639,7 +707,7 @@ def main():
     result = None
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cpu = cpu_baseline(wl)
             except Exception as e:  # report, never hide
@@ -696,6 +764,9 @@ def main():
             },
             "cpu_baseline": cpu,
         }
+        result["full"] = args.full
+        if not args.full:  # not measured in a plain run: left out rather than null
+            del result["bitexact_vs_reference"], result["cpu_baseline"], result["roofline"]["launch_us"]
         if warm:
             result["warm"] = warm
         if scaling_ref:

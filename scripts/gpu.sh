@@ -4,8 +4,8 @@
 # steps:
 #   tests            the whole -m gpu suite, then smoke()
 #   tests:EXPR       the -m gpu tests selected by -k EXPR
-#   bench:W          bench.py --workload W (cfg2 with the CPU baseline)
-#   kt:W             rocprofv3 kernel trace + stats of bench.py --workload W
+#   bench:W          bench.py --full --workload W (cfg2 with the CPU baseline)
+#   kt:W             rocprofv3 kernel trace + stats of bench.py --full --workload W
 #   traffic:W        FETCH_SIZE and WRITE_SIZE passes (separate runs) -> traffic_W.json
 #   pmcsum:W         the two SQ counter passes over bench.py W -> pmc_summary.json (scripts/pmc_summary.py)
 #   pmc:W:C1,C2,...  one PMC pass (counters within one pass's limits) over kbench W
@@ -49,12 +49,12 @@ for st in "$@"; do
 	bench)
 		cpu=--no-cpu-baseline
 		[ "$w" = cfg2 ] && cpu=
-		timeout -k 10 400 python bench.py --workload $w $cpu >$O/bench_$w.json 2>$O/bench_$w.err || { tail $O/bench_$w.err; exit 1; }
+		timeout -k 10 400 python bench.py --full --workload $w $cpu >$O/bench_$w.json 2>$O/bench_$w.err || { tail $O/bench_$w.err; exit 1; }
 		python3 -c "import json; d=json.load(open('$O/bench_$w.json')); r=d['roofline']; print('$w', d['ms_per_step'], d['value'], d['bitexact_vs_reference'], r['avg_launch_ms_hip_events'], r['frac'], r.get('launch_us'))"
 		;;
 	kt)
 		timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$w -o kt -- python3 bench.py \
-			--workload $w --no-cpu-baseline --no-warm >$O/kt_$w.log 2>&1 || { tail $O/kt_$w.log; exit 1; }
+			--full --workload $w --no-cpu-baseline --no-warm >$O/kt_$w.log 2>&1 || { tail $O/kt_$w.log; exit 1; }
 		python3 scripts/launch_stats.py $O/kt_$w/kt_kernel_trace.csv $(kern $w)
 		# the 25 launches after bench.py's 5 untimed warmups (its 20 timed steps
 		# and the first 5 of its separate per-launch pass)
