@@ -272,6 +272,21 @@ uint32_t airs_dev_memset(struct airs_dev_engine *e, void *dst, int v, size_t byt
 uint32_t airs_dev_d2d_rows(struct airs_dev_engine *e, void *dst, size_t dpitch, const void *src, size_t spitch,
 			   size_t width, size_t rows);
 
+/* Host-side launch counters of the process (every engine, every thread),
+ * counted where the kernel is launched: which kernel family and look-back
+ * mode a call took.  Copies the first min(n, AIRS_STAT_COUNT) counters to out
+ * and returns AIRS_STAT_COUNT.  For tests; nothing in the library reads them. */
+enum airs_launch_stat {
+	AIRS_STAT_RICE_FRAME_LB1 = 0, /* rice_kernel, frames, lbmode bit 0 set (scalar look-back from sif 16) */
+	AIRS_STAT_RICE_FRAME_LB0 = 1, /* rice_kernel, frames, lbmode 0 (vector look-back) */
+	AIRS_STAT_RICE_STREAM = 2,    /* rice_kernel, payload-only stream */
+	AIRS_STAT_RICE_AUTO = 3,      /* rice_kernel with the candidate barrier (CMP_GPU_AUTO_RICE) */
+	AIRS_STAT_ENCODE = 4,         /* encode_kernel, frames (its fused AUTO form included) */
+	AIRS_STAT_ENCODE_STREAM = 5,  /* encode_kernel, payload-only stream */
+	AIRS_STAT_COUNT = 6
+};
+uint32_t airs_dev_launch_stats(uint64_t *out, uint32_t n);
+
 /* non-zero when a HIP device is usable */
 int airs_dev_available(void);
 const char *airs_dev_last_error(void);

@@ -546,5 +546,8 @@ bool rice_encode(const KArgs &k, uint32_t pre, hipStream_t s, bool stream);
 bool rice_auto_encode(const KArgs &k, uint32_t pre, hipStream_t s);
 void stream_encode(const KArgs &k, uint32_t sample_bytes, uint32_t pre, uint32_t enc, bool rice, bool full,
 		   uint32_t grid, hipStream_t s);
+// host-side launch counters (airs_dev_launch_stats, airs_dev.h), one increment
+// at each launch site
+void launch_count(uint32_t which);
 
 } // namespace airs

@@ -1163,6 +1163,9 @@ bool rice_encode(const KArgs &k, uint32_t pre, hipStream_t s, bool stream)
 	else
 		kern = pre == PRE_DIFF ? rice_kernel<PRE_DIFF, false> : rice_kernel<PRE_NONE, false>;
 	hipLaunchKernelGGL(kern, dim3(ka.num_segs), dim3(RWG), lds, s, ka);
+	launch_count(stream		  ? AIRS_STAT_RICE_STREAM
+		     : (ka.lbmode & 1u) ? AIRS_STAT_RICE_FRAME_LB1
+					: AIRS_STAT_RICE_FRAME_LB0);
 	return true;
 }
 
@@ -1193,6 +1196,7 @@ bool rice_auto_encode(const KArgs &k, uint32_t pre, hipStream_t s)
 		hipLaunchKernelGGL((rice_kernel<PRE_DIFF, false, true>), dim3(grid), dim3(RWG), lds, s, ka);
 	else
 		hipLaunchKernelGGL((rice_kernel<PRE_NONE, false, true>), dim3(grid), dim3(RWG), lds, s, ka);
+	launch_count(AIRS_STAT_RICE_AUTO);
 	return true;
 }
 

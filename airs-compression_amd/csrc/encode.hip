@@ -36,6 +36,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 
 #include "airs_dev.h"
 
@@ -1139,6 +1140,22 @@ extern "C" void airs_dev_set_debug(uint32_t bits, const char *timeline_path)
 }
 #endif
 
+// launch counters (airs_dev.h enum airs_launch_stat): host only, relaxed
+static std::atomic<uint64_t> g_launch_stats[AIRS_STAT_COUNT];
+namespace airs
+{
+void launch_count(uint32_t which)
+{
+	g_launch_stats[which].fetch_add(1u, std::memory_order_relaxed);
+}
+} // namespace airs
+extern "C" uint32_t airs_dev_launch_stats(uint64_t *out, uint32_t n)
+{
+	for (uint32_t i = 0; out && i < n && i < AIRS_STAT_COUNT; i++)
+		out[i] = g_launch_stats[i].load(std::memory_order_relaxed);
+	return AIRS_STAT_COUNT;
+}
+
 static uint32_t hip_fail(hipError_t e, const char *what)
 {
 	snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
@@ -1441,6 +1458,7 @@ static void launch_encode(const KArgs &k, bool full, uint32_t grid, hipStream_t 
 				launch_segments(encode_kernel<W, PRE, ENC, RICE, MODEL, true, true>, k, grid, lds, s);
 			else
 				launch_segments(encode_kernel<W, PRE, ENC, RICE, MODEL, false, true>, k, grid, lds, s);
+			launch_count(AIRS_STAT_ENCODE);
 			return;
 		}
 	}
@@ -1454,6 +1472,7 @@ static void launch_encode(const KArgs &k, bool full, uint32_t grid, hipStream_t 
 			return;
 	}
 	const size_t lds = (size_t)seg_images(W, MODEL) * (k.img_words + 4u) * 4u;
+	launch_count(AIRS_STAT_ENCODE);
 #ifdef AIRS_EXP_ONLY
 	// experiment builds: only the benchmark kernels (u16/i16, DIFF, ZERO, Rice, FULL)
 	if constexpr (!(W == 2 && PRE == PRE_DIFF && ENC == ENC_ZERO && RICE && MODEL == 0)) {
@@ -1981,6 +2000,7 @@ extern "C" uint32_t airs_dev_encode_stream(struct airs_dev_engine *e, const void
 		return 0;
 	}
 	stream_encode(k, sample_bytes, preprocessing, encoder_type, rice, full, spf, e->stream);
+	launch_count(AIRS_STAT_ENCODE_STREAM);
 	HIPCHECK(hipGetLastError());
 	return 0;
 }

@@ -12,9 +12,14 @@ The data are chosen for the kernel's special steps:
     holds, so the segment is stored chunk by chunk after its look-back;
   * constant frames (every sample the shortest code) and the extreme mapped
     value 65535.
-Frames of 40 segments put the scalar first look-back round (16 granules)
-and the vector rounds behind it to work.  Bit-exact, with the clock-derived
-identifier bytes 8-13 masked (one context: frame f is its f-th primary pass).
+Frames of 40 segments put the vector look-back's first round (its 16
+newest granules and the tail through scalar loads) and the vector rounds
+behind it to work: these batches of 5, 3 and 2 frames are no multiple of 8,
+so the launch's lbmode is 0 and the all-scalar look-back (rice_lookback_s)
+never runs here; test_gpu_rice_lookback.py covers it.  The launch counters
+(airs_dev_launch_stats) assert which kernel ran.  Bit-exact, with the
+clock-derived identifier bytes 8-13 masked (one context: frame f is its f-th
+primary pass).
 Reference: lib/compress/cmp.c:296-312, encoder.c:327-351,
 bitstream_writer.h:124-158."""
 import zlib
@@ -23,6 +28,8 @@ import numpy as np
 import pytest
 
 from conftest import load_pkg
+from rice_helpers import ENCODE, LB0, Launches
+from rice_helpers import frame as _frame, gpu as _gpu, mask as _mask, oracle as _oracle
 
 pytestmark = pytest.mark.gpu
 api = load_pkg().cmpapi
@@ -37,76 +44,6 @@ def eng(prod):
     e = prod.engine()
     yield e
     e.close()
-
-
-def _frame(rng, kind, n, k, data):
-    if data == "laplace":
-        x = np.round(rng.laplace(0, 2.0 ** k, n)).astype(np.int64)
-        x = np.cumsum(x) if rng.random() < 0.5 else x
-    elif data == "outliers":
-        x = np.round(rng.laplace(0, 2.0 ** k, n)).astype(np.int64) + 16384
-        idx = rng.integers(0, n, max(1, n // 700))
-        x[idx] = rng.integers(0, 65536, idx.size)
-        x[::4099] = 0x8000 + x[::4099]  # an outlier at every alignment
-    elif data == "uniform":
-        x = rng.integers(0, 65536, n)
-    elif data == "const":
-        x = np.full(n, int(rng.integers(0, 65536)), dtype=np.int64)
-    else:  # extreme: the largest mapped value, NONE and DIFF
-        x = np.where(np.arange(n) % 2 == 0, 32767, -32768).astype(np.int64)
-        x[rng.integers(0, n, 50)] = 0
-    x = x & 0xFFFF
-    return x.astype(np.uint16) if kind == "u16" else x.astype(np.uint16).view(np.int16)
-
-
-def _oracle(orc, kind, pre, g, frames, checksum):
-    want = []
-    for x in frames:
-        ctx = api.CmpContext()
-        prm = P(primary_preprocessing=pre, primary_encoder_type=api.ENCODER_GOLOMB_ZERO, primary_encoder_param=g,
-                checksum_enabled=checksum)
-        assert not api.is_error(orc.initialise(ctx, prm))
-        cap = orc.compress_bound(2 * x.size)
-        dst = api.aligned_empty(cap)
-        r = orc.compress(kind, ctx, dst, cap, x)
-        assert not api.is_error(r), api.error_name(r)
-        want.append(bytes(dst[:r]))
-    return want
-
-
-def _gpu(prod, eng, kind, pre, g, frames, checksum):
-    import torch
-    n, nf = frames[0].size, len(frames)
-    stride = 2 * n
-    host = np.zeros(nf * stride, dtype=np.uint8)
-    for f, x in enumerate(frames):
-        host[f * stride:(f + 1) * stride] = np.ascontiguousarray(x).view(np.uint8)
-    src = torch.from_numpy(host).cuda()
-    cap = prod.compress_bound(2 * n)
-    dstride = (cap + 7) // 8 * 8
-    dst = torch.full((nf * dstride,), 0xAB, dtype=torch.uint8, device="cuda")
-    sizes = torch.zeros(nf, dtype=torch.int32, device="cuda")
-    ctxs = (api.CmpContext * 1)()
-    prm = P(primary_preprocessing=pre, primary_encoder_type=api.ENCODER_GOLOMB_ZERO, primary_encoder_param=g,
-            checksum_enabled=checksum)
-    assert not api.is_error(prod.initialise(ctxs[0], prm))
-    torch.cuda.synchronize()
-    r = eng.compress(ctxs, nf, kind, src.data_ptr(), stride, 2 * n, dst.data_ptr(), dstride, cap, sizes.data_ptr(), 0)
-    assert r == 0, api.error_name(r)
-    assert eng.synchronize() == 0
-    sz = sizes.cpu().numpy().astype(np.uint32)
-    out = dst.cpu().numpy()
-    got = []
-    for f in range(nf):
-        assert not api.is_error(int(sz[f])), api.error_name(int(sz[f]))
-        got.append(bytes(out[f * dstride:f * dstride + int(sz[f])]))
-    return got
-
-
-def _mask(b):
-    b = bytearray(b)
-    b[8:14] = b"\0" * 6
-    return bytes(b)
 
 
 CASES = []
@@ -127,7 +64,10 @@ def test_rice_kernel_vs_oracle(prod, eng, orc, k, pre, data):
         n = spf * SEG
         frames = [_frame(rng, kind, n, k, data) for _ in range(nf)]
         want = _oracle(orc, kind, pre, 1 << k, frames, checksum)
-        got = _gpu(prod, eng, kind, pre, 1 << k, frames, checksum)
+        with Launches(prod) as l:
+            got = _gpu(prod, eng, kind, pre, 1 << k, frames, checksum)
+        # one launch: the Rice kernel (lbmode 0: 5, 3 or 2 frames) up to k = 7, encode_kernel past it
+        l.only(LB0 if k <= 7 else ENCODE, 1)
         bad = [f for f in range(nf) if _mask(got[f]) != _mask(want[f])]
         assert not bad, (spf, bad, [(len(got[f]), len(want[f])) for f in bad])
 

@@ -13,6 +13,7 @@ import pytest
 
 import streams
 from conftest import load_pkg
+from rice_helpers import RICE_STREAM, Launches
 
 pytestmark = pytest.mark.gpu
 api = load_pkg().cmpapi
@@ -100,7 +101,7 @@ def test_stream_capacity_and_arguments(eng):
 
 
 @pytest.mark.parametrize("k", range(0, 8))
-def test_stream_rice_kernel_vs_oracle(eng, k):
+def test_stream_rice_kernel_vs_oracle(prod, eng, k):
     """Streams the Rice/ZERO frame kernel takes (16-bit,
     GOLOMB_ZERO with g = 2^k, k <= 7, whole 16 Ki-sample segments, STREAM
     mode: no header, the first payload bit at 0): laplace noise at the scale
@@ -122,9 +123,13 @@ def test_stream_rice_kernel_vs_oracle(eng, k):
             x = (v & 0xFFFF).astype(np.uint16) if kind == "u16" else (v & 0xFFFF).astype(np.uint16).view(np.int16)
             for pre in (0, 1):
                 want = streams.oracle_stream(x, kind, pre, 1, 1 << k, 0)
-                got = gpu_stream(eng, x, kind, pre, 1, 1 << k, 0)
+                with Launches(prod) as l:
+                    got = gpu_stream(eng, x, kind, pre, 1, 1 << k, 0)
+                l.only(RICE_STREAM, 1)  # the Rice kernel's stream launch, not encode_kernel's
                 if got != want:
                     bad.append((m, data, pre, got[0], want[0]))
     assert not bad, bad
-    s, _ = gpu_stream(eng, x, kind, 1, 1, 1 << k, 0, cap=want[0] - 1)
+    with Launches(prod) as l:
+        s, _ = gpu_stream(eng, x, kind, 1, 1, 1 << k, 0, cap=want[0] - 1)
+    l.only(RICE_STREAM, 1)
     assert api.error_name(s) == "DST_TOO_SMALL"
