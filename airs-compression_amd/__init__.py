@@ -22,6 +22,7 @@ LIB_PATH = os.path.join(PKG_DIR, "lib", "libairscmp.so")
 GPU_U16, GPU_I16, GPU_I16_IN_I32 = 0, 1, 2
 GPU_AUTO_RICE = 0x1
 REPORT_DRAWS = 0x8  # CMP_GPU_REPORT_DRAWS
+SEQ_MODEL_IN = 0x1  # CMP_GPU_SEQ_MODEL_IN (cmp_gpu_decompress_sequences)
 LAYOUT_ROUNDROBIN, LAYOUT_BLOCK, LAYOUT_STREAMS = 0, 1, 2  # enum cmp_gpu_layout
 GATHER_PATCH_IDS = 0x1  # CMP_GPU_GATHER_PATCH_IDS
 OPT_EXCLUSIVE = 1  # cmp_gpu_engine_set_option (include/cmp_gpu.h)
@@ -91,6 +92,27 @@ class GpuDecodeBatch(ctypes.Structure):
     ]
 
 
+class GpuDecodeSeqBatch(ctypes.Structure):
+    """struct cmp_gpu_decode_seq_batch (include/cmp_gpu.h)."""
+    _fields_ = [
+        ("type", c_int),
+        ("src", c_void_p),
+        ("src_stride", c_uint64),
+        ("src_capacity", c_uint32),
+        ("num_ctx", c_uint32),
+        ("frames_per_ctx", c_uint32),
+        ("dst", c_void_p),
+        ("dst_stride", c_uint64),
+        ("dst_samples", c_uint32),
+        ("status", c_void_p),
+        ("model", c_void_p),
+        ("model_stride", c_uint64),
+        ("model_n", c_void_p),
+        ("checksum_ok", c_void_p),
+        ("flags", c_uint32),
+    ]
+
+
 class AirsLib(CmpLib):
     """CmpLib plus the cmp_gpu.h device batch API."""
 
@@ -113,6 +135,8 @@ class AirsLib(CmpLib):
         L.cmp_gpu_synthesize.restype = c_uint32
         L.cmp_gpu_decompress.argtypes = [c_void_p, POINTER(GpuDecodeBatch)]
         L.cmp_gpu_decompress.restype = c_uint32
+        L.cmp_gpu_decompress_sequences.argtypes = [c_void_p, POINTER(GpuDecodeSeqBatch)]
+        L.cmp_gpu_decompress_sequences.restype = c_uint32
         L.cmp_gpu_encode_stream.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32,
                                             c_uint32, c_void_p, c_uint32, c_void_p]
         L.cmp_gpu_encode_stream.restype = c_uint32
@@ -199,6 +223,20 @@ class GpuEngine:
                            dst=dst_ptr, dst_stride=dst_stride, dst_samples=dst_samples, status=status_ptr,
                            model=model_ptr or None, model_stride=model_stride)
         return self.lib.lib.cmp_gpu_decompress(self.handle, ctypes.byref(b))
+
+    def decompress_sequences(self, kind: str, src_ptr: int, src_stride: int, src_capacity: int, num_ctx: int,
+                             frames_per_ctx: int, dst_ptr: int, dst_stride: int, dst_samples: int,
+                             status_ptr: int, model_ptr: int = 0, model_stride: int = 0, model_n_ptr: int = 0,
+                             checksum_ok_ptr: int = 0, flags: int = 0) -> int:
+        """cmp_gpu_decompress_sequences over device pointers: num_ctx sequences of
+        frames_per_ctx frames, MODEL frames decoded against the model rebuilt
+        from the frames before them (flags: SEQ_MODEL_IN)."""
+        b = GpuDecodeSeqBatch(type=KIND_TO_GPU[kind], src=src_ptr or None, src_stride=src_stride,
+                              src_capacity=src_capacity, num_ctx=num_ctx, frames_per_ctx=frames_per_ctx,
+                              dst=dst_ptr or None, dst_stride=dst_stride, dst_samples=dst_samples,
+                              status=status_ptr or None, model=model_ptr or None, model_stride=model_stride,
+                              model_n=model_n_ptr or None, checksum_ok=checksum_ok_ptr or None, flags=flags)
+        return self.lib.lib.cmp_gpu_decompress_sequences(self.handle, ctypes.byref(b))
 
     def encode_stream(self, kind: str, src_ptr: int, num_samples: int, preprocessing: int, encoder_type: int,
                       encoder_param: int, encoder_outlier: int, dst_ptr: int, dst_capacity: int,

@@ -22,10 +22,11 @@
  *
  * Decompression (the reference's default mode prints "Decompression not
  * implemented yet", airspacecli.c:421-423) is an extension here: the frames
- * of each .air input are decoded on the GPU with cmp_gpu_decompress() and
- * written back as big-endian 16-bit samples: runs of frames other than MODEL
- * as one batch, each MODEL frame alone, against the model rebuilt from the
- * frames before it.
+ * of each .air input are decoded on the GPU and written back as big-endian
+ * 16-bit samples.  Each chunk of frames (up to BATCH_BYTES), MODEL frames
+ * included, is one cmp_gpu_decompress_sequences() call: the model is rebuilt
+ * on the device and carried from chunk to chunk there, and every frame that
+ * has a checksum is verified against it.
  */
 #include <errno.h>
 #include <getopt.h>
@@ -576,28 +577,12 @@ static uint32_t be24(const uint8_t *p)
 	return (uint32_t)p[0] << 16 | (uint32_t)p[1] << 8 | p[2];
 }
 
-/* model after a frame: the samples (primary pass) or the weighted update
- * of the u16 model (reference cmp.c:304-311, is_unsigned) */
-static void next_model(uint16_t *model, const uint16_t *x, size_t n, int is_model_frame, uint32_t rate)
-{
-	size_t i;
-
-	if (!is_model_frame) {
-		memcpy(model, x, 2 * n);
-		return;
-	}
-	for (i = 0; i < n; i++)
-		model[i] = (uint16_t)(((uint32_t)model[i] * rate + (uint32_t)x[i] * (16u - rate)) >> 4);
-}
-
 static int decompress_file(struct job *j, struct dev *d, int fi)
 {
 	uint8_t *raw, *out = NULL;
-	size_t size, pos, total = 0;
+	size_t size, pos, total = 0, model_cap = 0;
 	int owned, r = -1;
-	uint16_t *model = NULL;
-	size_t model_n = 0;
-	void *d_model = NULL;
+	void *d_model = NULL, *d_model_n = NULL;
 
 	if (load_file(j->in[fi], &raw, &size, &owned))
 		return -1;
@@ -617,22 +602,22 @@ static int decompress_file(struct job *j, struct dev *d, int fi)
 	out = xmalloc(total);
 	if (dev_open(d))
 		goto out;
-	if (dev_reserve(&d->sizes, &d->sizes_cap, 64))
-		goto out;
+	/* samples of model the context holds (none yet), kept on the device */
+	if (hipMalloc(&d_model_n, 4) != hipSuccess || hipMemset(d_model_n, 0, 4) != hipSuccess)
+		goto gpu_fail;
 	{
 		size_t o = 0;
 
 		for (pos = 0; pos < size;) {
-			/* a run: one MODEL frame (it needs the frame before it), or
-			 * consecutive other frames, decoded as one batch */
-			const uint32_t pre0 = raw[pos + 15] >> 4;
+			/* a chunk: consecutive frames, MODEL frames included, decoded as
+			 * one sequence; the model carries on to the next chunk on the device */
 			size_t q = pos, nrun = 0, cap = 24, nmax = 1, dstride, i;
-			struct cmp_gpu_decode_batch b;
-			uint8_t *stage;
+			struct cmp_gpu_decode_seq_batch b;
+			uint8_t *stage, *ck;
 			uint16_t *x;
 			uint32_t *st, e;
 
-			for (;;) {
+			while (q < size) {
 				const uint32_t fs = be24(raw + q + 2), n = be24(raw + q + 5) / 2u;
 				const size_t c = fs < 24u ? 24u : ((size_t)fs + 7u) & ~(size_t)7u;
 				const size_t ncap = c > cap ? c : cap, nn = n > nmax ? n : nmax;
@@ -643,14 +628,27 @@ static int decompress_file(struct job *j, struct dev *d, int fi)
 				nmax = nn;
 				nrun++;
 				q += fs;
-				if (pre0 == CMP_PREPROCESS_MODEL || q >= size || (raw[q + 15] >> 4) == CMP_PREPROCESS_MODEL)
-					break;
 			}
 			dstride = (2u * nmax + 15u) & ~(size_t)15u; /* 16-byte rows: vector stores */
+			/* statuses, then one verification byte per frame */
 			if (dev_reserve(&d->src, &d->src_cap, nrun * cap) ||
 			    dev_reserve(&d->dst, &d->dst_cap, nrun * dstride) ||
-			    dev_reserve(&d->sizes, &d->sizes_cap, 4u * nrun))
+			    dev_reserve(&d->sizes, &d->sizes_cap, 5u * nrun))
 				goto out;
+			if (nmax > model_cap) { /* a larger model buffer; what it holds moves over */
+				void *m = NULL;
+
+				if (hipMalloc(&m, dstride) != hipSuccess)
+					goto gpu_fail;
+				e = !d_model ||
+				    hipMemcpy(m, d_model, 2u * model_cap, hipMemcpyDeviceToDevice) == hipSuccess;
+				if (d_model)
+					hipFree(d_model);
+				d_model = m;
+				model_cap = nmax;
+				if (!e)
+					goto gpu_fail;
+			}
 			stage = calloc(nrun, cap);
 			if (!stage) {
 				log_errno("Memory allocation failed");
@@ -667,39 +665,32 @@ static int decompress_file(struct job *j, struct dev *d, int fi)
 			if (!e)
 				goto gpu_fail;
 			memset(&b, 0, sizeof(b));
+			b.type = CMP_GPU_U16; /* the reference CLI writes u16 frames only */
 			b.src = d->src;
 			b.src_stride = cap;
 			b.src_capacity = (uint32_t)cap;
-			b.num_frames = (uint32_t)nrun;
+			b.num_ctx = 1;
+			b.frames_per_ctx = (uint32_t)nrun;
 			b.dst = d->dst;
 			b.dst_stride = dstride;
 			b.dst_samples = (uint32_t)nmax;
 			b.status = d->sizes;
-			if (pre0 == CMP_PREPROCESS_MODEL) {
-				const uint32_t n = be24(raw + pos + 5) / 2u;
-
-				if (model_n != n) {
-					log_msg(LOG_ERROR, "%s: MODEL frame without a preceding frame of its size",
-						display(j->in[fi]));
-					goto out;
-				}
-				if (!d_model && hipMalloc(&d_model, 2u * (size_t)n + 16u) != hipSuccess)
-					goto gpu_fail;
-				if (hipMemcpy(d_model, model, 2u * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
-					goto gpu_fail;
-				b.model = d_model;
-				b.model_stride = 2u * (uint64_t)n + 16u;
-			}
-			e = cmp_gpu_decompress(d->eng, &b);
+			b.model = d_model;
+			b.model_stride = dstride;
+			b.model_n = d_model_n;
+			b.checksum_ok = (uint8_t *)d->sizes + 4u * nrun;
+			b.flags = CMP_GPU_SEQ_MODEL_IN;
+			e = cmp_gpu_decompress_sequences(d->eng, &b);
 			if (!cmp_is_error(e))
 				e = cmp_gpu_synchronize(d->eng);
 			if (cmp_is_error(e)) {
 				log_cmp(e, "Decompression failed for %s", display(j->in[fi]));
 				goto out;
 			}
-			st = xmalloc(4u * nrun);
+			st = xmalloc(5u * nrun);
+			ck = (uint8_t *)st + 4u * nrun;
 			x = xmalloc(nrun * dstride);
-			if (hipMemcpy(st, d->sizes, 4u * nrun, hipMemcpyDeviceToHost) != hipSuccess ||
+			if (hipMemcpy(st, d->sizes, 5u * nrun, hipMemcpyDeviceToHost) != hipSuccess ||
 			    hipMemcpy(x, d->dst, nrun * dstride, hipMemcpyDeviceToHost) != hipSuccess) {
 				free(st);
 				free(x);
@@ -708,11 +699,23 @@ static int decompress_file(struct job *j, struct dev *d, int fi)
 			for (i = 0; i < nrun; i++) {
 				const uint32_t n = be24(raw + pos + 5) / 2u;
 				const uint16_t *xi = (const uint16_t *)((const uint8_t *)x + i * dstride);
+				const enum cmp_error code = cmp_get_error_code(st[i]);
+				int bad = 1;
 				uint32_t k;
 
-				if (cmp_is_error(st[i]) || st[i] != n) {
+				if ((raw[pos + 15] >> 4) == CMP_PREPROCESS_MODEL &&
+				    (code == CMP_ERR_PARAMS_INVALID || code == CMP_ERR_SRC_SIZE_MISMATCH))
+					log_msg(LOG_ERROR, "%s: MODEL frame without a preceding frame of its size",
+						display(j->in[fi]));
+				else if (cmp_is_error(st[i]) || st[i] != n)
 					log_cmp(cmp_is_error(st[i]) ? st[i] : (uint32_t) - (int32_t)CMP_ERR_INT_BITSTREAM,
 						"Decompression failed for %s", display(j->in[fi]));
+				else if (ck[i] == 2u)
+					log_msg(LOG_ERROR, "%s: checksum mismatch in the frame at byte %lu",
+						display(j->in[fi]), (unsigned long)pos);
+				else
+					bad = 0;
+				if (bad) {
 					free(st);
 					free(x);
 					goto out;
@@ -722,18 +725,6 @@ static int decompress_file(struct job *j, struct dev *d, int fi)
 					out[o + 2u * k + 1u] = (uint8_t)xi[k];
 				}
 				o += 2u * (size_t)n;
-				if (i + 1u == nrun) { /* the model the next frame may need */
-					if (model_n != n) {
-						free(model);
-						model = xmalloc(2u * (size_t)n + 2u);
-						model_n = n;
-						if (d_model) {
-							hipFree(d_model);
-							d_model = NULL;
-						}
-					}
-					next_model(model, xi, n, pre0 == CMP_PREPROCESS_MODEL, raw[pos + 16]);
-				}
 				pos += be24(raw + pos + 2);
 			}
 			free(st);
@@ -772,7 +763,8 @@ gpu_fail:
 out:
 	if (d_model)
 		hipFree(d_model);
-	free(model);
+	if (d_model_n)
+		hipFree(d_model_n);
 	free(out);
 	if (owned)
 		free(raw);

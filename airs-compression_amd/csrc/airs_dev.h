@@ -194,6 +194,11 @@ uint32_t airs_dev_pack_frames(struct airs_dev_engine *e, const void *src, uint64
 uint32_t airs_dev_checksum(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
 			   uint32_t sample_bytes, uint32_t n, uint32_t num_frames,
 			   const uint32_t *frame_list, uint32_t *out);
+/* the same over frames of different sizes: frame f has frame_n[f] samples
+ * (device; 0: no checksum wanted, out[f] is not written), n_max the largest */
+uint32_t airs_dev_checksum_n(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
+			     uint32_t sample_bytes, uint32_t n_max, const uint32_t *frame_n,
+			     uint32_t num_frames, uint32_t *out);
 
 /* per-frame Rice parameter (build-defined rule): out_g[f] = 2^k
  * for the batch frames f = frame_list[j] (AIRS_NO_FRAME: none) or
@@ -260,6 +265,28 @@ uint32_t airs_dev_patch_ids_at(struct airs_dev_engine *e, void *data, const uint
 uint32_t airs_dev_decode(struct airs_dev_engine *e, const void *src, uint64_t src_stride, uint32_t src_cap,
 			 uint32_t num_frames, uint16_t *dst, uint64_t dst_stride, uint32_t dst_samples,
 			 uint32_t *status, const uint16_t *model, uint64_t model_stride);
+
+/* whole sequences (cmp_gpu_decompress_sequences, see cmp_gpu.h): the same
+ * pipeline over all num_ctx * fpc frames up to the residuals in dst, then one
+ * walk per context with its model in registers.  model / model_n / checksum_ok
+ * may be NULL; model_in: the contexts start from model / model_n. */
+struct airs_decode_seq {
+	const void *src;
+	uint64_t src_stride;
+	uint32_t src_cap;
+	uint32_t num_ctx, fpc;
+	uint16_t *dst;
+	uint64_t dst_stride;
+	uint32_t dst_samples;
+	uint32_t *status;
+	uint16_t *model;
+	uint64_t model_stride;
+	uint32_t *model_n;
+	uint8_t *checksum_ok;
+	uint32_t is_unsigned;    /* u16: zero-extend in the model update (cmp.c:132-142) */
+	uint32_t model_in;
+};
+uint32_t airs_dev_decode_seq(struct airs_dev_engine *e, const struct airs_decode_seq *q);
 
 /* plain memory helpers on the engine stream */
 void *airs_dev_malloc(size_t bytes);

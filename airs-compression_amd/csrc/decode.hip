@@ -52,6 +52,7 @@ namespace airsdec {
 
 struct DecInfo {
 	uint32_t n, nbits, hdr_bits, enc, pre, k, g, cutoff, outlier, nsub, wmax, status;
+	uint32_t aux; // sequence number | model rate << 8 | checksum bit << 16 (the sequence walk)
 };
 
 struct DecArgs {
@@ -72,6 +73,7 @@ struct DecArgs {
 	uint16_t *tile_sum;
 	const uint16_t *model; // MODEL frames: frame f's model at model + f * model_stride bytes
 	uint64_t model_stride;
+	uint32_t seq; // sequence mode: MODEL frames get their model from the frames before them
 };
 
 __device__ __forceinline__ uint32_t bswap32(uint32_t v)
@@ -233,11 +235,15 @@ __global__ void dec_hdr_kernel(DecArgs a)
 		st = ERRV(E_INT_HDR);
 	else if (I.pre > 3u) // no such preprocessing (cmp.h: NONE, DIFF, IWT, MODEL)
 		st = ERRV(E_INT_HDR);
-	else if (I.pre == 3u && !a.model) // MODEL without its model
+	else if (I.pre == 3u && !a.model && !a.seq) // MODEL without its model
 		st = ERRV(E_PARAMS_INVALID);
+	else if (a.seq && I.pre == 3u && b[16] > 16u) // no such model rate (cmp.h: CMP_MAX_MODEL_RATE)
+		st = ERRV(E_INT_HDR);
 	else if (I.enc > 2u)
 		st = ERRV(E_INT_ENCODER);
 	I.n = osize / 2u;
+	if (!st)
+		I.aux = (uint32_t)b[14] | (ext ? (uint32_t)b[16] << 8 : 0u) | ck << 16;
 	if (!st && I.n > a.dst_samples)
 		st = ERRV(E_GENERIC);
 	if (!st && I.enc != 0u) {
@@ -266,6 +272,8 @@ __global__ void dec_hdr_kernel(DecArgs a)
 	atomicMax(a.maxsub, I.nsub);
 	if (!st && I.pre == 2u)
 		atomicOr(a.maxsub + 2, 1u); // some frame needs the inverse IWT
+	if (a.seq && !st && ck)
+		atomicMax(a.maxsub + 3, I.n); // the largest frame that carries a checksum
 }
 
 // decode [start, end) of the stream from LDS: exit position and codeword count
@@ -756,6 +764,200 @@ __global__ void dec_status_kernel(DecArgs a)
 	a.status[f] = I.status ? I.status : I.n;
 }
 
+// ---------------------------------------------------------------------
+// Whole sequences (airs_dev_decode_seq): context c owns frames c*fpc ..
+// c*fpc + fpc-1 in acquisition order.  After the batch pipeline above every
+// frame that parsed holds its residuals (MODEL) or its samples (NONE, DIFF,
+// IWT) in dst.  dec_seq_plan_kernel walks each context's headers and decides
+// per frame what the chain does with it; dec_seq_chain_kernel then rebuilds
+// the models (cmp.c:120-142, 304-311) and the MODEL frames' samples.
+// ---------------------------------------------------------------------
+#define E_SRC_SIZE_MISMATCH 42u
+#define SEQ_SKIP 0u  // failed frame: nothing to do, the context holds no model after it
+#define SEQ_STORE 1u // not MODEL: the model becomes the frame's samples
+#define SEQ_MODEL 2u // x = r + model, model = blend(x, model)
+#define SEQ_WG 256u
+#define SEQ_TILE (8u * SEQ_WG) // samples a chain workgroup covers: 8 per lane
+
+struct SeqArgs {
+	uint32_t num_ctx, fpc;
+	uint16_t *model; // context c's model at model + c * model_stride bytes (or NULL)
+	uint64_t model_stride;
+	uint32_t *model_n; // [num_ctx] (or NULL)
+	uint32_t model_in;
+	uint2 *ops;        // [frames]: op | rate << 8, n
+	uint32_t *ctx_n;   // [num_ctx]: samples of model each context holds at the end
+	uint32_t *frame_n; // [frames] (or NULL): n of the frames to verify, else 0
+	const uint32_t *ck; // [frames]: XXH32 of the decoded samples (where frame_n is set)
+	uint8_t *ck_ok;
+};
+
+// one thread per context: the failure rules of cmp_gpu.h in frame order
+__global__ void dec_seq_plan_kernel(DecArgs a, SeqArgs q)
+{
+	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= q.num_ctx)
+		return;
+	uint32_t have = q.model_in ? q.model_n[c] : 0u; // samples of model held, 0: none
+	if (have > a.dst_samples) // not a model of this batch's buffers
+		have = 0u;
+	for (uint32_t i = 0; i < q.fpc; i++) {
+		const uint32_t f = c * q.fpc + i;
+		const uint32_t n = a.info[f].n, pre = a.info[f].pre, aux = a.info[f].aux;
+		uint32_t st = a.info[f].status, op = SEQ_SKIP;
+		if (!st && pre == 3u) {
+			if (!have)
+				st = ERRV(E_PARAMS_INVALID);
+			else if (have != n)
+				st = ERRV(E_SRC_SIZE_MISMATCH);
+			else
+				op = SEQ_MODEL;
+		} else if (!st) {
+			op = SEQ_STORE;
+		}
+		have = st ? 0u : n;
+		a.status[f] = st ? st : n;
+		q.ops[f] = make_uint2(op | (aux & 0xFF00u), n);
+		if (q.frame_n)
+			q.frame_n[f] = !st && (aux >> 16) ? n : 0u;
+	}
+	q.ctx_n[c] = have;
+	if (q.model_n)
+		q.model_n[c] = have;
+}
+
+// 8 consecutive 16-bit values as four words: one 16-byte access when the row
+// allows it and all 8 exist, else the first cnt of them one by one
+__device__ __forceinline__ uint4 seq_load8(const uint16_t *p, uint32_t cnt, bool vec)
+{
+	if (vec && cnt == 8u)
+		return *reinterpret_cast<const uint4 *>(p);
+	uint32_t v[8];
+#pragma unroll
+	for (uint32_t k = 0; k < 8u; k++)
+		v[k] = k < cnt ? p[k] : 0u;
+	return make_uint4(v[0] | v[1] << 16, v[2] | v[3] << 16, v[4] | v[5] << 16, v[6] | v[7] << 16);
+}
+
+__device__ __forceinline__ void seq_store8(uint16_t *p, const uint32_t (&v)[8], uint32_t cnt, bool vec)
+{
+	if (vec && cnt == 8u) {
+		*reinterpret_cast<uint4 *>(p) = make_uint4((v[0] & 0xFFFFu) | v[1] << 16, (v[2] & 0xFFFFu) | v[3] << 16,
+							   (v[4] & 0xFFFFu) | v[5] << 16, (v[6] & 0xFFFFu) | v[7] << 16);
+		return;
+	}
+#pragma unroll
+	for (uint32_t k = 0; k < 8u; k++)
+		if (k < cnt)
+			p[k] = (uint16_t)v[k];
+}
+
+// a 16-bit value as the model update sees it (cmp.c:132-142)
+template <bool SGN>
+__device__ __forceinline__ uint32_t seq_ext(uint32_t v)
+{
+	return SGN ? (uint32_t)(int32_t)(int16_t)v : v & 0xFFFFu;
+}
+
+// The chain.  Grid: sample tiles x contexts; each lane owns 8 consecutive
+// samples and keeps their model values (the low halves of m[]) in registers
+// over the context's frames.  A frame's op, n and rate are the same for the
+// whole workgroup and are read through a block-uniform index.  The loads of
+// different frames do not depend on each other: the rows of the next two
+// frames are requested before the current frame's arithmetic.  Per sample the
+// products are below 2^21 in magnitude, so the 24-bit multiplies apply.
+template <bool SGN>
+__global__ __launch_bounds__(SEQ_WG) void dec_seq_chain_kernel(DecArgs a, SeqArgs q, const uint2 *__restrict__ all_ops)
+{
+	const uint32_t c = blockIdx.y, f0 = c * q.fpc, i0 = (blockIdx.x * SEQ_WG + threadIdx.x) * 8u;
+	const bool vd = (((uintptr_t)a.dst | a.dst_stride) & 15u) == 0;
+	const bool vm = (((uintptr_t)q.model | q.model_stride) & 15u) == 0;
+	// q.ops as a restrict argument of its own: nothing the kernel stores can
+	// alias it, which is what lets the per-frame reads be scalar loads
+	const uint2 *ops = all_ops + f0;
+	uint16_t *row0 = a.dst + (uint64_t)f0 * (a.dst_stride / 2u) + i0;
+	uint16_t *mrow = q.model + (uint64_t)c * (q.model_stride / 2u) + i0;
+	uint32_t m[8];
+	{
+		const uint32_t cnt = q.model_in && i0 < a.dst_samples ? min(8u, a.dst_samples - i0) : 0u;
+		const uint4 w = seq_load8(mrow, cnt, vm);
+		const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+		for (uint32_t k = 0; k < 4u; k++) {
+			m[2 * k] = ww[k];
+			m[2 * k + 1] = ww[k] >> 16;
+		}
+	}
+	// this lane's share of a frame: 0 when the frame is skipped or ends before it
+	auto count = [&](uint2 o) { return (o.x & 0xFFu) == SEQ_SKIP || i0 >= o.y ? 0u : min(8u, o.y - i0); };
+	auto row = [&](uint32_t i) { return row0 + (uint64_t)i * (a.dst_stride / 2u); };
+	auto op_at = [&](uint32_t i) { return i < q.fpc ? ops[i] : make_uint2(SEQ_SKIP, 0u); };
+	auto step = [&](uint32_t i, uint2 o, uint4 w) { // frame i with its row's 8 values in w
+		const uint32_t cnt = count(o);
+		if (!cnt)
+			return;
+		const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+		if ((o.x & 0xFFu) == SEQ_STORE) {
+#pragma unroll
+			for (uint32_t k = 0; k < 4u; k++) {
+				m[2 * k] = ww[k];
+				m[2 * k + 1] = ww[k] >> 16;
+			}
+			return;
+		}
+		const uint32_t rate = (o.x >> 8) & 0x1Fu, drate = 16u - rate;
+		uint32_t x[8];
+#pragma unroll
+		for (uint32_t k = 0; k < 8u; k++) {
+			const uint32_t r = k & 1u ? ww[k >> 1] >> 16 : ww[k >> 1];
+			const uint32_t mk = seq_ext<SGN>(m[k]);
+			x[k] = seq_ext<SGN>(r + mk);
+			if (SGN)
+				m[k] = (uint32_t)((__mul24((int32_t)mk, (int32_t)rate) + __mul24((int32_t)x[k], (int32_t)drate)) >> 4);
+			else
+				m[k] = (__umul24(mk, rate) + __umul24(x[k], drate)) >> 4;
+		}
+		seq_store8(row(i), x, cnt, vd);
+	};
+	// three frames per trip, so that the rows in flight rotate through three
+	// register sets without copies (a copy would wait for its load)
+	uint2 oa = op_at(0), ob = op_at(1), oc;
+	uint4 wa = seq_load8(row(0), count(oa), vd), wb = seq_load8(row(1), count(ob), vd), wc;
+	for (uint32_t i = 0; i < q.fpc; i += 3u) {
+		oc = op_at(i + 2u);
+		wc = seq_load8(row(i + 2u), count(oc), vd);
+		step(i, oa, wa);
+		oa = op_at(i + 3u);
+		wa = seq_load8(row(i + 3u), count(oa), vd);
+		step(i + 1u, ob, wb);
+		ob = op_at(i + 4u);
+		wb = seq_load8(row(i + 4u), count(ob), vd);
+		step(i + 2u, oc, wc);
+	}
+	if (q.model) {
+		const uint32_t cn = q.ctx_n[c];
+		if (i0 < cn)
+			seq_store8(mrow, m, min(8u, cn - i0), vm);
+	}
+}
+
+// stored checksum (the frame's last four bytes, big-endian) against the XXH32
+// of the decoded samples
+__global__ void dec_seq_verify_kernel(DecArgs a, SeqArgs q)
+{
+	const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+	if (f >= a.num_frames)
+		return;
+	uint8_t ok = 0;
+	if (q.frame_n[f]) {
+		const uint8_t *b = a.src + (uint64_t)f * a.src_stride;
+		const uint8_t *t = b + ((((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 8) | b[4]) - 4u);
+		const uint32_t stored = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
+		ok = stored == q.ck[f] ? 1u : 2u;
+	}
+	q.ck_ok[f] = ok;
+}
+
 } // namespace airsdec
 
 using namespace airsdec;
@@ -769,9 +971,15 @@ using namespace airsdec;
 // Decode num_frames frames (device) into 16-bit samples (device); status[f] =
 // samples decoded or an error value.  Synchronises with the host to size the
 // parse and to test for a settled parse.
-extern "C" uint32_t airs_dev_decode(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
-				   uint32_t src_cap, uint32_t num_frames, uint16_t *dst, uint64_t dst_stride,
-				   uint32_t dst_samples, uint32_t *status, const uint16_t *model, uint64_t model_stride)
+//
+// With a sequence description (airs_dev_decode_seq) the frames are num_ctx
+// sequences of fpc: MODEL frames are taken without a model, dec_model_kernel
+// gives way to the plan and the chain, which write the statuses, and the
+// checksums are verified when asked for.  No further synchronisation.
+static uint32_t decode_frames(struct airs_dev_engine *e, const void *src, uint64_t src_stride, uint32_t src_cap,
+			      uint32_t num_frames, uint16_t *dst, uint64_t dst_stride, uint32_t dst_samples,
+			      uint32_t *status, const uint16_t *model, uint64_t model_stride,
+			      const struct airs_decode_seq *seq)
 {
 	if (!e || !src || !dst || !status || !num_frames || (src_stride & 7u) || ((uintptr_t)src & 7u) ||
 	    ((uintptr_t)dst & 1u) || (dst_stride & 1u))
@@ -789,17 +997,21 @@ extern "C" uint32_t airs_dev_decode(struct airs_dev_engine *e, const void *src, 
 	a.status = status;
 	a.model = model;
 	a.model_stride = model_stride;
-	// frame info + the largest subsequence count
-	uint8_t *hdr = (uint8_t *)airs_dev_scratch(e, AIRS_NSLOT - 2, (size_t)num_frames * sizeof(DecInfo) + 64u);
+	a.seq = seq ? 1u : 0u;
+	// frame info + the largest subsequence count (+ the sequence walk's arrays)
+	const size_t info_bytes = ((size_t)num_frames * sizeof(DecInfo) + 7u) & ~(size_t)7u;
+	const size_t seq_bytes = seq ? (size_t)num_frames * 16u + (size_t)seq->num_ctx * 4u : 0u;
+	uint8_t *hdr = (uint8_t *)airs_dev_scratch(e, AIRS_NSLOT - 2, info_bytes + 64u + seq_bytes);
 	if (!hdr)
 		return ERRV(E_GENERIC);
 	a.info = (DecInfo *)hdr;
-	a.maxsub = (uint32_t *)(hdr + (size_t)num_frames * sizeof(DecInfo));
+	a.maxsub = (uint32_t *)(hdr + info_bytes);
 	a.changed = a.maxsub + 1;
-	DCHECK(hipMemsetAsync(a.maxsub, 0, 12, s));
+	DCHECK(hipMemsetAsync(a.maxsub, 0, 16, s));
 	hipLaunchKernelGGL(dec_hdr_kernel, dim3((num_frames + 255u) / 256u), dim3(256), 0, s, a);
-	uint32_t hv[3] = {0, 0, 0}; // largest subsequence count, (changed), any IWT frame
-	DCHECK(hipMemcpyAsync(hv, a.maxsub, 12, hipMemcpyDeviceToHost, s));
+	// largest subsequence count, (changed), any IWT frame, largest frame with a checksum (sequences)
+	uint32_t hv[4] = {0, 0, 0, 0};
+	DCHECK(hipMemcpyAsync(hv, a.maxsub, 16, hipMemcpyDeviceToHost, s));
 	DCHECK(hipStreamSynchronize(s));
 	const uint32_t msub = hv[0];
 	const bool any_iwt = hv[2] != 0u;
@@ -871,7 +1083,61 @@ extern "C" uint32_t airs_dev_decode(struct airs_dev_engine *e, const void *src, 
 			}
 		}
 	}
-	hipLaunchKernelGGL(dec_status_kernel, dim3((num_frames + 255u) / 256u), dim3(256), 0, s, a);
+	if (!seq) {
+		hipLaunchKernelGGL(dec_status_kernel, dim3((num_frames + 255u) / 256u), dim3(256), 0, s, a);
+		DCHECK(hipGetLastError());
+		return 0;
+	}
+	SeqArgs q;
+	memset(&q, 0, sizeof(q));
+	q.num_ctx = seq->num_ctx;
+	q.fpc = seq->fpc;
+	q.model = seq->model;
+	q.model_stride = seq->model_stride;
+	q.model_n = seq->model_n;
+	q.model_in = seq->model_in;
+	uint8_t *sq = hdr + info_bytes + 64u;
+	q.ops = (uint2 *)sq;
+	q.frame_n = seq->checksum_ok ? (uint32_t *)(sq + (size_t)num_frames * 8u) : nullptr;
+	uint32_t *ck = (uint32_t *)(sq + (size_t)num_frames * 12u);
+	q.ck = ck;
+	q.ctx_n = (uint32_t *)(sq + (size_t)num_frames * 16u);
+	q.ck_ok = seq->checksum_ok;
+	hipLaunchKernelGGL(dec_seq_plan_kernel, dim3((q.num_ctx + 63u) / 64u), dim3(64), 0, s, a, q);
+	const dim3 cg((dst_samples + SEQ_TILE - 1u) / SEQ_TILE, q.num_ctx);
+	if (cg.x) {
+		if (seq->is_unsigned)
+			hipLaunchKernelGGL(dec_seq_chain_kernel<false>, cg, dim3(SEQ_WG), 0, s, a, q, (const uint2 *)q.ops);
+		else
+			hipLaunchKernelGGL(dec_seq_chain_kernel<true>, cg, dim3(SEQ_WG), 0, s, a, q, (const uint2 *)q.ops);
+	}
+	if (q.ck_ok) {
+		// frames of different sizes in one call: the checksum kernels take the
+		// per-frame sample counts the plan wrote (0: nothing to verify)
+		if (hv[3]) {
+			const uint32_t r = airs_dev_checksum_n(e, dst, dst_stride, 2u, hv[3], q.frame_n, num_frames, ck);
+			if (r)
+				return r;
+		}
+		hipLaunchKernelGGL(dec_seq_verify_kernel, dim3((num_frames + 255u) / 256u), dim3(256), 0, s, a, q);
+	}
 	DCHECK(hipGetLastError());
 	return 0;
+}
+
+extern "C" uint32_t airs_dev_decode(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
+				   uint32_t src_cap, uint32_t num_frames, uint16_t *dst, uint64_t dst_stride,
+				   uint32_t dst_samples, uint32_t *status, const uint16_t *model, uint64_t model_stride)
+{
+	return decode_frames(e, src, src_stride, src_cap, num_frames, dst, dst_stride, dst_samples, status, model,
+			     model_stride, nullptr);
+}
+
+extern "C" uint32_t airs_dev_decode_seq(struct airs_dev_engine *e, const struct airs_decode_seq *q)
+{
+	if (!q || !q->num_ctx || !q->fpc || (uint64_t)q->num_ctx * q->fpc > 65535u || (q->model && !q->model_n) ||
+	    (q->model_in && !q->model) || ((uintptr_t)q->model & 1u) || (q->model_stride & 1u))
+		return ERRV(E_GENERIC);
+	return decode_frames(e, q->src, q->src_stride, q->src_cap, q->num_ctx * q->fpc, q->dst, q->dst_stride,
+			     q->dst_samples, q->status, nullptr, 0, q);
 }

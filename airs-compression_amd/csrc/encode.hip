@@ -485,18 +485,21 @@ __device__ __forceinline__ uint32_t xxh_round_pre(uint32_t acc, uint32_t yp2)
 // per group of 16 frames, for every 4 rounds, 64 chains x 16 bytes
 // (chain = 4 (frame % 16) + accumulator), so one 16-byte load per lane reads
 // 1 KiB contiguous.  S4 = stripes rounded up to 4.
-template <int W>
+// VN: frames of different sizes in one launch (the decoder's verification):
+// frame f has frame_n[f] samples (0: none, nothing is written for it), n is
+// the largest of them and sizes Y.
+template <int W, bool VN>
 __global__ __launch_bounds__(256) void ck_pre_kernel(const uint8_t *src, uint64_t stride, uint32_t n,
 						     uint32_t num_frames, const uint32_t *frame_list, uint32_t S4,
-						     uint32_t *Y)
+						     uint32_t *Y, const uint32_t *frame_n)
 {
 	// a workgroup covers 16 frames x 16 round quads, frame fastest: the 64
 	// lanes of a wave write 4 KiB of Y contiguous (their four stores fill it)
-	const uint32_t stripes = n / 8u;
 	const uint32_t lf = blockIdx.x * 16u + (threadIdx.x & 15u);
 	if (lf >= num_frames)
 		return;
 	const uint32_t frame = frame_list ? frame_list[lf] : lf;
+	const uint32_t stripes = (VN ? frame_n[frame] : n) / 8u;
 	const uint8_t *f = src + (uint64_t)frame * stride;
 	// rounds 4 r4 .. 4 r4 + 3 (grid-stride: gridDim.y is capped)
 	for (uint32_t r4 = blockIdx.y * 16u + (threadIdx.x >> 4); 4u * r4 < stripes; r4 += gridDim.y * 16u) {
@@ -538,14 +541,15 @@ __global__ __launch_bounds__(256) void ck_pre_kernel(const uint8_t *src, uint64_
 	}
 }
 
-template <int W>
-__global__ __launch_bounds__(64) void ck_chain_kernel(const uint8_t *src, uint64_t stride, uint32_t n,
+template <int W, bool VN>
+__global__ __launch_bounds__(64) void ck_chain_kernel(const uint8_t *src, uint64_t stride, uint32_t n0,
 						      uint32_t num_frames, const uint32_t *frame_list, uint32_t S4,
-						      const uint32_t *Y, uint32_t *out)
+						      const uint32_t *Y, uint32_t *out, const uint32_t *frame_n)
 {
 	const uint32_t lane = threadIdx.x, q = lane & 3u;
 	const uint32_t lf = blockIdx.x * 16u + (lane >> 2);
-	const bool valid = lf < num_frames;
+	const uint32_t n = !VN ? n0 : lf < num_frames ? frame_n[frame_list ? frame_list[lf] : lf] : 0u;
+	const bool valid = lf < num_frames && n;
 	const uint32_t len = 2u * n;
 	const uint32_t stripes = len >= 16u ? n / 8u : 0u;
 	const uint32_t seed = 419764627u;
@@ -2005,9 +2009,10 @@ extern "C" uint32_t airs_dev_encode_stream(struct airs_dev_engine *e, const void
 	return 0;
 }
 
-extern "C" uint32_t airs_dev_checksum(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
-				      uint32_t sample_bytes, uint32_t n, uint32_t num_frames,
-				      const uint32_t *frame_list, uint32_t *out)
+template <bool VN>
+static uint32_t checksum_launch(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
+				uint32_t sample_bytes, uint32_t n, uint32_t num_frames, const uint32_t *frame_list,
+				uint32_t *out, const uint32_t *frame_n)
 {
 	if (!e || !n || !num_frames)
 		return ERRV(E_GENERIC);
@@ -2025,20 +2030,36 @@ extern "C" uint32_t airs_dev_checksum(struct airs_dev_engine *e, const void *src
 	if (stripes) {
 		const dim3 pg(grid.x, min((S4 / 4u + 15u) / 16u, 65535u));
 		if (sample_bytes == 2)
-			hipLaunchKernelGGL(ck_pre_kernel<2>, pg, dim3(256), 0, e->stream, (const uint8_t *)src, src_stride,
-					   n, num_frames, frame_list, S4, Y);
+			hipLaunchKernelGGL((ck_pre_kernel<2, VN>), pg, dim3(256), 0, e->stream, (const uint8_t *)src,
+					   src_stride, n, num_frames, frame_list, S4, Y, frame_n);
 		else
-			hipLaunchKernelGGL(ck_pre_kernel<4>, pg, dim3(256), 0, e->stream, (const uint8_t *)src, src_stride,
-					   n, num_frames, frame_list, S4, Y);
+			hipLaunchKernelGGL((ck_pre_kernel<4, VN>), pg, dim3(256), 0, e->stream, (const uint8_t *)src,
+					   src_stride, n, num_frames, frame_list, S4, Y, frame_n);
 	}
 	if (sample_bytes == 2)
-		hipLaunchKernelGGL(ck_chain_kernel<2>, grid, dim3(64), 0, e->stream, (const uint8_t *)src, src_stride, n,
-				   num_frames, frame_list, S4, (const uint32_t *)Y, out);
+		hipLaunchKernelGGL((ck_chain_kernel<2, VN>), grid, dim3(64), 0, e->stream, (const uint8_t *)src,
+				   src_stride, n, num_frames, frame_list, S4, (const uint32_t *)Y, out, frame_n);
 	else
-		hipLaunchKernelGGL(ck_chain_kernel<4>, grid, dim3(64), 0, e->stream, (const uint8_t *)src, src_stride, n,
-				   num_frames, frame_list, S4, (const uint32_t *)Y, out);
+		hipLaunchKernelGGL((ck_chain_kernel<4, VN>), grid, dim3(64), 0, e->stream, (const uint8_t *)src,
+				   src_stride, n, num_frames, frame_list, S4, (const uint32_t *)Y, out, frame_n);
 	HIPCHECK(hipGetLastError());
 	return 0;
+}
+
+extern "C" uint32_t airs_dev_checksum(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
+				      uint32_t sample_bytes, uint32_t n, uint32_t num_frames,
+				      const uint32_t *frame_list, uint32_t *out)
+{
+	return checksum_launch<false>(e, src, src_stride, sample_bytes, n, num_frames, frame_list, out, nullptr);
+}
+
+extern "C" uint32_t airs_dev_checksum_n(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
+					uint32_t sample_bytes, uint32_t n_max, const uint32_t *frame_n,
+					uint32_t num_frames, uint32_t *out)
+{
+	if (!frame_n)
+		return ERRV(E_GENERIC);
+	return checksum_launch<true>(e, src, src_stride, sample_bytes, n_max, num_frames, nullptr, out, frame_n);
 }
 
 // the sliced selection over frame f at src + (f / div) * stride, or ptrs[j]

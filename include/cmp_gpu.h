@@ -133,7 +133,8 @@ uint32_t cmp_gpu_compress(struct cmp_gpu_engine *engine, struct cmp_context *ctx
  * cmp_compress_* / cmp_gpu_compress back into their 16-bit samples (the low
  * halves, for i16-in-i32 sources).  Frames of every preprocessing mode and
  * encoder; MODEL frames need the model each was encoded against (MODEL frames
- * without one get CMP_ERR_PARAMS_INVALID).  The checksum is not verified. */
+ * without one get CMP_ERR_PARAMS_INVALID).  The checksum is not verified
+ * (cmp_gpu_decompress_sequences below rebuilds the models and verifies). */
 struct cmp_gpu_decode_batch {
 	const void *src;        /* device; frame i at src + i*src_stride, 8-byte aligned */
 	uint64_t src_stride;    /* bytes, multiple of 8, >= src_capacity */
@@ -151,6 +152,68 @@ struct cmp_gpu_decode_batch {
  * batch->status.  Synchronises with the host (the parse is sized from the
  * headers and repeated until it settles). */
 uint32_t cmp_gpu_decompress(struct cmp_gpu_engine *engine, const struct cmp_gpu_decode_batch *batch);
+
+/*
+ * Whole sequences: num_ctx contexts of frames_per_ctx frames each, in the
+ * order cmp_gpu_compress writes them, decoded in one call.  The model a MODEL
+ * frame was encoded against is a function of the samples before it, so it is
+ * rebuilt here as the reference's encoder builds it (cmp.c:120-142, 304-311),
+ * per context and on the device: every frame is parsed in one batch, then one
+ * kernel walks each context's frames with the model in registers.
+ *
+ * Per context the frames decode in order, each by what its header says:
+ *   - a frame that is not MODEL (NONE, DIFF, IWT; a raw fallback frame in
+ *     mid-sequence, cmp.c:380-392, is one) decodes on its own; the context's
+ *     model then is its samples;
+ *   - a MODEL frame: x = r + model (int16 wrap), then model[i] =
+ *     (model[i]*rate + x[i]*(16-rate)) >> 4 in int32, truncated to 16 bits,
+ *     rate from the frame's header (above 16: CMP_ERR_INT_HDR), x and model
+ *     zero-extended for CMP_GPU_U16 and sign-extended otherwise;
+ *   - a MODEL frame whose context holds no model gets CMP_ERR_PARAMS_INVALID,
+ *     one whose context holds a model of another size
+ *     CMP_ERR_SRC_SIZE_MISMATCH;
+ *   - a frame that fails for any reason keeps its error value, and its
+ *     context holds no model until its next frame that is not MODEL decodes;
+ *     other contexts are unaffected.
+ *
+ * checksum_ok (optional) asks for verification: for every frame that decoded
+ * and whose header has the checksum bit, the XXH32 of the decoded samples as
+ * big-endian 16-bit words (header.c:137-163) is compared with the frame's
+ * last four bytes.  A mismatch is reported there only; status is not changed.
+ *
+ * Returns CMP_ERR_NO_ERROR or a call-level error (CMP_ERR_GENERIC: NULL or
+ * misaligned pointers, bad strides, more than 65535 frames, model without
+ * model_n, CMP_GPU_SEQ_MODEL_IN without model, unknown flags), before anything
+ * reaches the device.  Synchronises with the host exactly where
+ * cmp_gpu_decompress does (the parse rounds), never per frame or acquisition.
+ * Build-defined extension.
+ */
+#define CMP_GPU_SEQ_MODEL_IN 0x1u /* contexts start from the models in batch->model */
+
+struct cmp_gpu_decode_seq_batch {
+	enum cmp_gpu_sample_type type; /* U16: zero-extending model update; I16 / I16_IN_I32: sign-extending
+					* (cmp.c:132-142); the output is 16-bit samples in every case */
+	const void *src;        /* as cmp_gpu_decode_batch */
+	uint64_t src_stride;
+	uint32_t src_capacity;
+	uint32_t num_ctx, frames_per_ctx; /* frame (c, a) is frame c*frames_per_ctx + a;
+					   * num_ctx*frames_per_ctx <= 65535 */
+	uint16_t *dst;          /* device; frame i's samples at dst + i*dst_stride bytes */
+	uint64_t dst_stride;    /* bytes, even, >= 2*dst_samples (16-byte rows are fastest) */
+	uint32_t dst_samples;   /* samples available per frame */
+	uint32_t *status;       /* device [frames]: samples decoded, or an error value */
+	uint16_t *model;        /* device or NULL: context c's model at model + c*model_stride bytes,
+				 * dst_samples samples each; read with CMP_GPU_SEQ_MODEL_IN, always
+				 * written with the model each context holds after its last frame */
+	uint64_t model_stride;  /* bytes, even, >= 2*dst_samples */
+	uint32_t *model_n;      /* device [num_ctx], required with model: samples of model held
+				 * (0: none); in with CMP_GPU_SEQ_MODEL_IN, always out */
+	uint8_t *checksum_ok;   /* device [frames] or NULL; non-NULL asks for verification:
+				 * 0 no checksum in the frame (or the frame failed), 1 match, 2 mismatch */
+	uint32_t flags;
+};
+
+uint32_t cmp_gpu_decompress_sequences(struct cmp_gpu_engine *engine, const struct cmp_gpu_decode_seq_batch *batch);
 
 /*
  * Payload-only stream: the num_samples samples at src (device) encoded as ONE
