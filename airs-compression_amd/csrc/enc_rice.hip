@@ -85,6 +85,14 @@ namespace airs {
 #ifndef AIRS_RICE_STORE_AUX
 #define AIRS_RICE_STORE_AUX 2
 #endif
+// the segment's fixed work taken off the vector ALU, a bit
+// per item so that an A/B build can leave one out: 1 = the wave totals after
+// B1 in scalar code, 2 = the scalar look-back's window in halves of 8
+// granules, 4 = the segment's last 32 bits in scalar code
+#ifndef AIRS_RICE_FW
+#define AIRS_RICE_FW 7
+#endif
+#define AIRS_RICE_UNI(x) ((AIRS_RICE_FW & 1) ? (uint32_t)__builtin_amdgcn_readfirstlane(x) : (x))
 #define RICE_KMAX 7u       // largest k this kernel takes (pairs of typical codes fit 32 bits)
 constexpr uint32_t RWG = AIRS_RICE_WG;      // threads per workgroup
 constexpr uint32_t RNW = RWG / 64u;         // waves per workgroup
@@ -305,7 +313,7 @@ __device__ __forceinline__ uint2 rice_lookback(const KArgs &a, uint32_t gseg, ui
 // and a scalar load that misses the scalar cache sees the newest value).
 // A vector poll queues behind the CU's sample loads (~2.4 us per re-poll on
 // a loaded CU); a scalar poll does not (~1 us).  Windows of
-// 16 granules, newest first, evaluated in scalar code: granules are summed
+// 8 granules (SW below), newest first, evaluated in scalar code: granules are summed
 // down to the nearest inclusive one; an unpublished granule is re-polled
 // after s_sleep, with the sum of the newer ones kept; a window of aggregates
 // only moves on to the next one at once.  After AIRS_RICE_SPOLL polls the
@@ -319,7 +327,12 @@ __device__ __forceinline__ uint2 rice_lookback(const KArgs &a, uint32_t gseg, ui
 __device__ __forceinline__ uint2 rice_lookback_s(const KArgs &a, uint32_t gseg, uint32_t sif, uint32_t lane)
 {
 	typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-	constexpr uint32_t SW = AIRS_RICE_SWIN;
+	// A window of 16 granules takes 32 scalar registers, and the allocator
+	// paid for them with spills of values that live across the whole kernel,
+	// moved by every wave.  So the window is read in halves
+	// of 8 granules, newest first: the older half is loaded only when the
+	// newer one holds aggregates alone.
+	constexpr uint32_t SW = (AIRS_RICE_FW & 2) ? 8u : AIRS_RICE_SWIN;
 	auto sptr = [](const uint64_t *p) {
 		const uint64_t v = (uint64_t)(uintptr_t)p;
 		const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)v);
@@ -906,7 +919,29 @@ rice_kernel(KArgs a)
 	}
 
 	// ---- the segment's last 32 bits (wave 3: lanes 60-63, chunk 3) --------
-	if (!is_last && wid == RNW - 1) {
+	// Lane 63 owns the word and would need its neighbours only if its chunk
+	// held fewer than 32 bits (it does not: a codeword has at least two bits,
+	// the test below is a guard).  When none of its pairs exceeds 32 bits, its
+	// eight pairs and their lengths go to scalar registers and the word is
+	// formed in scalar code; otherwise the vector path below.
+	bool tail_s = false;
+	uint32_t tl0 = 0u, tl1 = 0u;
+	if ((AIRS_RICE_FW & 4) && !is_last && wid == RNW - 1) {
+		tl0 = __builtin_amdgcn_readlane(lp[RCH - 1][0], 63);
+		tl1 = __builtin_amdgcn_readlane(lp[RCH - 1][1], 63);
+		const uint32_t ov = ((tl0 + 0x1F1F1F1Fu) | (tl1 + 0x1F1F1F1Fu)) & 0x40404040u; // some L > 32
+		tail_s = ov == 0u && (uint32_t)__builtin_amdgcn_readlane(T[RCH - 1], 63) >= 32u;
+	}
+	if (tail_s) {
+		uint64_t acc = 0u;
+#pragma unroll
+		for (uint32_t j = 0; j < 8u; j++) {
+			const uint32_t L = ((j < 4u ? tl0 : tl1) >> (8u * (j & 3u))) & 0xFFu;
+			acc = (acc << L) | (uint32_t)__builtin_amdgcn_readlane(V[RCH - 1][j], 63);
+		}
+		if (lane == 63u)
+			gran_store(&a.tail[gseg], ((uint64_t)a.epoch << 32) | (uint32_t)acc);
+	} else if (!is_last && wid == RNW - 1) {
 		uint64_t acc = 0u;
 		const uint2 *tb = s_tab;
 #pragma unroll
@@ -946,13 +981,18 @@ rice_kernel(KArgs a)
 	uint32_t excl[RCH], tot[RCH], base[RCH];
 	uint32_t A = 0u;
 	{
+		// the wave sums are the same in every lane: into scalar registers once,
+		// so that the totals tt and the wave offsets oo below are scalar code
+		// and a lane only adds its own inc - T
 		uint32_t w01[RNW], w23[RNW];
 #pragma unroll
 		for (uint32_t w = 0; w < RNW; w += 4) {
 			const uint4 s01 = *reinterpret_cast<const uint4 *>(&s_wsum[0][w]);
 			const uint4 s23 = *reinterpret_cast<const uint4 *>(&s_wsum[1][w]);
-			w01[w] = s01.x, w01[w + 1] = s01.y, w01[w + 2] = s01.z, w01[w + 3] = s01.w;
-			w23[w] = s23.x, w23[w + 1] = s23.y, w23[w + 2] = s23.z, w23[w + 3] = s23.w;
+			w01[w] = AIRS_RICE_UNI(s01.x), w01[w + 1] = AIRS_RICE_UNI(s01.y);
+			w01[w + 2] = AIRS_RICE_UNI(s01.z), w01[w + 3] = AIRS_RICE_UNI(s01.w);
+			w23[w] = AIRS_RICE_UNI(s23.x), w23[w + 1] = AIRS_RICE_UNI(s23.y);
+			w23[w + 2] = AIRS_RICE_UNI(s23.z), w23[w + 3] = AIRS_RICE_UNI(s23.w);
 		}
 		// chunk totals can pass 2^16 across the four waves: carry-free halves
 		// of each wave's sum, added in 32 bits
@@ -1089,11 +1129,19 @@ rice_kernel(KArgs a)
 			a.needed[frame] = payload_bytes;
 	}
 	if (!STREAM && is_last && tid == 0) {
+		// the header's own fields are read from the kernel-argument segment
+		// here, where one lane of the frame's last segment needs them: loaded
+		// with the other arguments at the kernel's start, every wave kept them
+		// in spill lanes to the end
+		const __attribute__((address_space(4))) KArgs *ka =
+			(const __attribute__((address_space(4))) KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+		asm volatile("" : "+s"(ka));
+		const uint32_t checksum = ka->checksum, seq = ka->seq;
 		const uint32_t P = s_misc[2];
 		const uint32_t n = a.n;
 		const uint32_t payload_bytes = (P + A + 7u) >> 3;
-		const uint32_t size = payload_bytes + (a.checksum ? 4u : 0u);
-		if (a.checksum) {
+		const uint32_t size = payload_bytes + (checksum ? 4u : 0u);
+		if (checksum) {
 			const uint32_t ck = a.checksums[frame];
 			for (uint32_t b = 0; b < 4u; b++)
 				if (payload_bytes + b < cap)
@@ -1101,7 +1149,7 @@ rice_kernel(KArgs a)
 		}
 		const uint64_t id = a.ids ? a.ids[lf] : a.id_base + (uint64_t)lf * a.id_step;
 		uint32_t h[5];
-		header_words(h, size, 2u * n, id, a.seqs ? a.seqs[frame] : a.seq, PRE, a.checksum ? 1u : 0u, ENC_ZERO, 0u,
+		header_words(h, size, 2u * n, id, a.seqs ? a.seqs[frame] : seq, PRE, checksum ? 1u : 0u, ENC_ZERO, 0u,
 			     cd.g, cd.outlier);
 		if (((uintptr_t)fdst & 7u) == 0u && cap >= 20u) {
 			*reinterpret_cast<uint2 *>(fdst) = make_uint2(bswap32(h[0]), bswap32(h[1]));
