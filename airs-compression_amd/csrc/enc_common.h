@@ -3,8 +3,10 @@
 // enc_stream.hip: payload-only streams).  Reference citations as in encode.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "airs_dev.h"
+#include "airs_rcp.h"
 
 #ifndef AIRS_WG
 #define AIRS_WG 256
@@ -57,12 +59,27 @@ namespace airs {
 enum { PRE_NONE = 0, PRE_DIFF = 1, PRE_IWT = 2, PRE_MODEL = 3 };
 enum { ENC_RAW = 0, ENC_ZERO = 1, ENC_MULTI = 2 };
 
-struct KArgs {
+// Kernel arguments of the encode kernels.  The first 64 bytes are the front
+// block: everything rice_kernel needs to find its frame and issue its sample
+// loads, naturally aligned in one cache line of the kernel-argument segment,
+// so that one s_load_dwordx16 and one wait stand before the first sample load
+// (DESIGN.md 3.1.6).  KFRONT_* are its dword indices.
+struct alignas(64) KArgs {
 	const uint8_t *src;
+	uint64_t src_stride;
+	const uint32_t *frame_list;
+	uint32_t frame_add, frame_mul;
+	uint32_t segs_per_frame;
+	uint32_t nfr;     // frames of the launch (launch positions: num_segs / segs_per_frame)
+	uint32_t nfr_rcp; // airs_rcp_u32(nfr, blocks of the launch), 0: divide (airs_rcp.h)
+	uint32_t spf_rcp; // airs_rcp_u32(segs_per_frame, ...), rice_kernel's AUTO order
+	uint32_t dbg; // ablation switches (AIRS_DBG env, benchmarking only; 0 in production)
+	uint32_t front_rsv;
+	uint64_t *dbgts; // AIRS_DBG bit 65536 (ablation builds): per-segment timeline
+	// ---- end of the front block ----
 	uint8_t *dst;
 	uint8_t *model;
 	const uint64_t *model_ptrs;
-	const uint32_t *frame_list;
 	const uint32_t *frame_g;
 	const uint32_t *checksums;
 	const uint64_t *ids;
@@ -71,24 +88,35 @@ struct KArgs {
 	uint64_t *agg;   // per segment: (epoch<<1 | inclusive) << 32 | bits
 	uint64_t *tail;  // per segment: epoch << 32 | last 32 bits of the segment's stream
 	uint32_t *ticket;
-	uint64_t src_stride, dst_stride, model_stride;
-	uint32_t frame_add, frame_mul, model_div;
+	uint64_t dst_stride, model_stride;
+	uint32_t model_div;
 	uint32_t lbmode; // rice_kernel: bit 0 = every segment and its predecessors on one XCD (scalar look-back polls)
 	uint64_t id_base, id_step, fail_bit;
-	uint32_t n, segs_per_frame, num_segs, cap;
+	uint32_t n, num_segs, cap;
 	uint32_t g, outlier_param;
 	uint32_t model_mode, model_rate, is_unsigned, checksum;
 	uint32_t seq, pre_hdr, enc_hdr, model_rate_hdr;
 	uint32_t ticket_base, epoch;
 	uint32_t img_words; // LDS image size: AIRS_SEG * (longest codeword) / 32 + 4, multiple of 4
-	uint32_t dbg; // ablation switches (AIRS_DBG env, benchmarking only; 0 in production)
-	uint64_t *dbgts; // AIRS_DBG bit 65536 (ablation builds): per-segment timeline
 	// fused per-frame Rice selection (encode_kernel<..., AUTO>): per segment 16
 	// granules, epoch << 32 | sum over its samples of min((m+1) >> k, 16), k = 0..15
 	uint64_t *ktot;
 	// per batch frame header sequence numbers (device-planned launches), else seq
 	const uint8_t *seqs;
 };
+enum {
+	KFRONT_SRC = 0, KFRONT_SRC_STRIDE = 2, KFRONT_FRAME_LIST = 4, KFRONT_FRAME_ADD = 6, KFRONT_FRAME_MUL = 7,
+	KFRONT_SPF = 8, KFRONT_NFR = 9, KFRONT_NFR_RCP = 10, KFRONT_SPF_RCP = 11, KFRONT_DBG = 12, KFRONT_DBGTS = 14
+};
+static_assert(offsetof(KArgs, src) == 4 * KFRONT_SRC && offsetof(KArgs, src_stride) == 4 * KFRONT_SRC_STRIDE &&
+		      offsetof(KArgs, frame_list) == 4 * KFRONT_FRAME_LIST &&
+		      offsetof(KArgs, frame_add) == 4 * KFRONT_FRAME_ADD &&
+		      offsetof(KArgs, frame_mul) == 4 * KFRONT_FRAME_MUL &&
+		      offsetof(KArgs, segs_per_frame) == 4 * KFRONT_SPF && offsetof(KArgs, nfr) == 4 * KFRONT_NFR &&
+		      offsetof(KArgs, nfr_rcp) == 4 * KFRONT_NFR_RCP && offsetof(KArgs, spf_rcp) == 4 * KFRONT_SPF_RCP &&
+		      offsetof(KArgs, dbg) == 4 * KFRONT_DBG && offsetof(KArgs, dbgts) == 4 * KFRONT_DBGTS &&
+		      offsetof(KArgs, dst) == 64,
+	      "the front block is the first 64 bytes of KArgs");
 
 // frame_list entry of a launch position without a frame this launch
 #define AIRS_NO_FRAME 0xFFFFFFFFu
@@ -461,14 +489,18 @@ __device__ __forceinline__ uint32_t gt16_mask(uint32_t q)
 // slots of the realtime clock (100 MHz): 0 start, 1 aggregate published,
 // 2 look-back done, 3 look-back start, 4 segment done (wave 0); 5 look-back
 // rounds | retries << 32, 6 tail re-polls; slot 7 = HW_ID << 32 | XCC_ID.  scripts/ts_analyze.py.
+// Light timeline (bit 131072): slots 0 and 4, the shader clock at each in 1 and
+// 2, the shader clock at the kernel's entry in 3 (rice_kernel, dbg_stamp_entry).
 __device__ __forceinline__ void dbg_stamp(const KArgs &a, uint32_t gseg, uint32_t slot)
 {
 	if (DBG(131072u)) { // light timeline: slots 0 and 4 only, with the shader clock in 1 and 2
-		if (DBG(65536u) && a.dbgts && threadIdx.x == 0 && (slot == 0 || slot == 4)) {
+		// (and slot 5, wave 0's samples landed, with bit 262144; slot 3: dbg_stamp_entry)
+		if (DBG(65536u) && a.dbgts && threadIdx.x == 0 && (slot == 0 || slot == 4 || (slot == 5 && DBG(262144u)))) {
 			uint64_t t, c;
 			asm volatile("s_memrealtime %0\n s_memtime %1\n s_waitcnt lgkmcnt(0)" : "=s"(t), "=s"(c));
 			a.dbgts[8u * gseg + slot] = t;
-			a.dbgts[8u * gseg + (slot ? 2u : 1u)] = c;
+			if (slot != 5)
+				a.dbgts[8u * gseg + (slot ? 2u : 1u)] = c;
 			if (slot == 0) {
 				uint32_t hw, xcc;
 				asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
@@ -489,6 +521,28 @@ __device__ __forceinline__ void dbg_stamp(const KArgs &a, uint32_t gseg, uint32_
 			a.dbgts[8u * gseg + 7u] = ((uint64_t)hw << 32) | xcc;
 		}
 	}
+}
+
+// The light timeline's slot 3: the shader clock (s_memtime) read as the
+// kernel's first instruction, stored where slot 0 is stamped, so that slot 1
+// (the shader clock at slot 0) less slot 3 is the time a workgroup spends
+// between its entry and its first sample load
+__device__ __forceinline__ uint64_t dbg_entry_clock()
+{
+	uint64_t c = 0u;
+#if AIRS_ABLATE
+	// no wait here: every path to dbg_stamp_entry passes an s_waitcnt lgkmcnt(0)
+	// (the kernel arguments' at the latest), and a wait would lengthen the
+	// stretch that is measured
+	asm volatile("s_memtime %0" : "=s"(c));
+#endif
+	return c;
+}
+
+__device__ __forceinline__ void dbg_stamp_entry(const KArgs &a, uint32_t gseg, uint64_t c_entry)
+{
+	if (DBG(131072u) && DBG(65536u) && a.dbgts && threadIdx.x == 0)
+		a.dbgts[8u * gseg + 3u] = c_entry;
 }
 
 

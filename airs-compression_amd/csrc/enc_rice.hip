@@ -677,14 +677,16 @@ __device__ __forceinline__ void rice_pair_table(uint2 *pt, uint32_t k, uint32_t 
 // for DIFF the sample before each chunk's first (lane 0 of each wave uses it;
 // every lane loads, so the load needs no branch; 0 before the frame's first
 // sample, reference preprocess.c:268-300)
+typedef const __attribute__((address_space(1))) uint8_t *rice_src_t; // (global memory: no flat loads)
 template <int PRE>
-__device__ __forceinline__ void rice_load(const KArgs &a, const uint8_t *fsrc, uint32_t sif, uint32_t gseg, uint32_t tid,
+__device__ __forceinline__ void rice_load(const KArgs &a, rice_src_t fsrc, uint32_t sif, uint32_t gseg, uint32_t tid,
 					  uint4 (&raw)[RCH][2], uint32_t (&prevld)[RCH])
 {
 #pragma unroll
 	for (uint32_t c = 0; c < RCH; c++) {
 		const uint32_t first = sif * RSEGN + c * RCHUNK + tid * EPT;
-		const uint4 *p = reinterpret_cast<const uint4 *>(fsrc + (size_t)first * 2u);
+		const __attribute__((address_space(1))) u32x4 *p =
+			reinterpret_cast<const __attribute__((address_space(1))) u32x4 *>(fsrc + (size_t)first * 2u);
 		if (DBG(512u)) { // ablation: no HBM reads (noise of width ~64 made in registers)
 			uint32_t h = (first * 2654435761u) ^ (gseg * 40503u);
 			uint32_t wv[8];
@@ -696,13 +698,14 @@ __device__ __forceinline__ void rice_load(const KArgs &a, const uint8_t *fsrc, u
 			raw[c][0] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
 			raw[c][1] = make_uint4(wv[4], wv[5], wv[6], wv[7]);
 		} else {
-			raw[c][0] = p[0];
-			raw[c][1] = p[1];
+			const u32x4 r0 = p[0], r1 = p[1];
+			raw[c][0] = make_uint4(r0.x, r0.y, r0.z, r0.w);
+			raw[c][1] = make_uint4(r1.x, r1.y, r1.z, r1.w);
 		}
 		// (the caller zeroes it for the frame's first sample, at the use:
 		// a select here would make the compiler wait for the load)
 		if (PRE == PRE_DIFF)
-			prevld[c] = reinterpret_cast<const uint16_t *>(fsrc)[first ? first - 1u : 0u];
+			prevld[c] = reinterpret_cast<const __attribute__((address_space(1))) uint16_t *>(fsrc)[first ? first - 1u : 0u];
 		else
 			prevld[c] = 0u;
 	}
@@ -710,8 +713,9 @@ __device__ __forceinline__ void rice_load(const KArgs &a, const uint8_t *fsrc, u
 
 template <int PRE, bool STREAM, bool AUTO = false>
 __global__ __launch_bounds__(RWG) __attribute__((amdgpu_waves_per_eu(rice_wgpcu<PRE, AUTO>() * RWG / 256u, 8))) void
-rice_kernel(KArgs a)
+rice_kernel(KArgs a_in)
 {
+	const uint64_t c_entry = dbg_entry_clock(); // (ablation builds)
 	static_assert(!(AUTO && STREAM), "AUTO: frames only");
 	// 22-byte header (GOLOMB_ZERO); STREAM (cmp_gpu_encode_stream): one frame,
 	// payload only (no header, checksum or 24-bit size field)
@@ -727,33 +731,62 @@ rice_kernel(KArgs a)
 
 	const uint32_t tid = threadIdx.x, lane = tid & 63u;
 	const uint32_t wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const uint32_t nfr = a.num_segs / a.segs_per_frame;
+	// ---- the front block: the one read of the kernel-argument
+	// segment that stands before the sample loads, one 64-byte scalar load from
+	// the segment itself.  Every other field is read through the parameter
+	// where it is first used, after the sample loads are issued, so that its
+	// latency hides under the samples'.
+	typedef const __attribute__((address_space(4))) uint8_t *kseg_t;
+	typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+	const kseg_t kseg = (kseg_t)__builtin_amdgcn_kernarg_segment_ptr();
+	const u32x16 fb = *reinterpret_cast<const __attribute__((address_space(4))) u32x16 *>(kseg);
+	auto fb64 = [&fb](uint32_t i) { return ((uint64_t)fb[i + 1u] << 32) | fb[i]; };
+	const uint32_t spf = fb[KFRONT_SPF], nfr = fb[KFRONT_NFR];
+	KArgs a = a_in;
+	a.segs_per_frame = spf; // (the copies already in registers)
+	a.nfr = nfr;
+	a.dbg = fb[KFRONT_DBG];
+	if (AIRS_ABLATE)
+		a.dbgts = reinterpret_cast<uint64_t *>((uintptr_t)fb64(KFRONT_DBGTS));
 	// Frame-interleaved order (as encode_kernel): dispatch index d is segment
 	// d / nfr of launch frame d % nfr, so a frame's segments come in order.
 	// One segment per workgroup, d = the block index.  AUTO: frame-major and
 	// XCD-local instead (as encode_kernel's AUTO): frame 8 j + x takes blocks
 	// x + 8 (j spf + s), so that a frame's segments, which meet at the
 	// candidate barrier, are dispatched together on one XCD; the grid is padded
-	// to whole groups of 8 frames.
+	// to whole groups of 8 frames.  The divisions are multiplications by the
+	// host's reciprocals (airs_rcp.h); a reciprocal of 0 (a launch past the
+	// bound of the method) divides, by a scalar shift-and-subtract loop: the
+	// compiler lays that branch out in line, and the `/` operator's reciprocal
+	// sequence would stand in the text between the entry and the sample loads.
 	const uint32_t d = blockIdx.x;
 	uint32_t sif, lf;
 	if constexpr (AUTO) {
-		const uint32_t p = d >> 3;
-		sif = p % a.segs_per_frame;
-		lf = 8u * (p / a.segs_per_frame) + (d & 7u);
+		const uint32_t p = d >> 3, rcp = fb[KFRONT_SPF_RCP];
+		const uint32_t fq = __builtin_expect(rcp != 0u, 1) ? airs_rcp_div(p, spf, rcp) : airs_udiv_slow(p, spf);
+		sif = p - fq * spf;
+		lf = 8u * fq + (d & 7u);
 		if (lf >= nfr)
 			return; // padding block
 	} else {
-		sif = d / nfr;
+		const uint32_t rcp = fb[KFRONT_NFR_RCP];
+		sif = __builtin_expect(rcp != 0u, 1) ? airs_rcp_div(d, nfr, rcp) : airs_udiv_slow(d, nfr);
 		lf = d - sif * nfr;
 	}
-	const uint32_t gseg = lf * a.segs_per_frame + sif;
-	const uint32_t frame =
-		__builtin_amdgcn_readfirstlane(a.frame_list ? a.frame_list[lf] : a.frame_add + lf * a.frame_mul);
+	const uint32_t gseg = lf * spf + sif;
+	// (the launch's frame list and its samples are not written during the
+	// launch: the list is read as constant memory, a scalar load)
+	const __attribute__((address_space(4))) uint32_t *const flist =
+		reinterpret_cast<const __attribute__((address_space(4))) uint32_t *>((uintptr_t)fb64(KFRONT_FRAME_LIST));
+	uint32_t frame = fb[KFRONT_FRAME_ADD] + lf * fb[KFRONT_FRAME_MUL];
+	if (flist) // (one statement with its wait: the only other wait before the sample loads)
+		asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(frame) : "s"(flist + lf));
 	if (frame == AIRS_NO_FRAME)
 		return;
-	const uint8_t *const fsrc = a.src + (uint64_t)frame * a.src_stride;
+	const rice_src_t fsrc =
+		reinterpret_cast<rice_src_t>((uintptr_t)(fb64(KFRONT_SRC) + (uint64_t)frame * fb64(KFRONT_SRC_STRIDE)));
 	dbg_stamp(a, gseg, 0);
+	dbg_stamp_entry(a, gseg, c_entry);
 
 	// ---- phase 0: every load of the segment, then zero the arena ----------
 	uint4 raw[RCH][2];
@@ -1191,6 +1224,11 @@ bool rice_encode(const KArgs &k, uint32_t pre, hipStream_t s, bool stream)
 	const uint32_t nfr = k.num_segs / k.segs_per_frame;
 	ka.segs_per_frame = k.n / RSEGN;
 	ka.num_segs = nfr * ka.segs_per_frame;
+	// the front block's divisors for this kernel's own order: block d < num_segs
+	// is segment d / nfr of launch frame d % nfr
+	ka.nfr = nfr;
+	ka.nfr_rcp = airs_rcp_u32(nfr, ka.num_segs);
+	ka.spf_rcp = airs_rcp_u32(ka.segs_per_frame, ka.num_segs);
 	ka.img_words = pre == PRE_DIFF ? rice_arena_words(rice_wgpcu<PRE_DIFF, false>())
 				       : rice_arena_words(rice_wgpcu<PRE_NONE, false>());
 	// block b runs on XCD b mod 8 (round-robin placement, MI355X_MICROARCH.md):
@@ -1239,6 +1277,11 @@ bool rice_auto_encode(const KArgs &k, uint32_t pre, hipStream_t s)
 	ka.img_words = pre == PRE_DIFF ? rice_arena_words(rice_wgpcu<PRE_DIFF, true>())
 				       : rice_arena_words(rice_wgpcu<PRE_NONE, true>());
 	const uint32_t grid = (nfr + 7u) / 8u * 8u * ka.segs_per_frame;
+	// the front block's divisors: block d < grid has p = d >> 3 divided by the
+	// frame's segments
+	ka.nfr = nfr;
+	ka.nfr_rcp = airs_rcp_u32(nfr, grid);
+	ka.spf_rcp = airs_rcp_u32(ka.segs_per_frame, grid >> 3);
 	const size_t lds = (size_t)ka.img_words * 4u;
 	if (pre == PRE_DIFF)
 		hipLaunchKernelGGL((rice_kernel<PRE_DIFF, false, true>), dim3(grid), dim3(RWG), lds, s, ka);

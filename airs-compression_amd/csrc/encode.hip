@@ -1731,6 +1731,11 @@ extern "C" uint32_t airs_dev_encode(struct airs_dev_engine *e, const struct airs
 	k.n = L->n;
 	k.segs_per_frame = spf;
 	k.num_segs = (uint32_t)segs;
+	// (the front block's divisors, KArgs in enc_common.h; the Rice kernel's
+	// launches set them again for their own segment count)
+	k.nfr = spf ? k.num_segs / spf : 0u;
+	k.nfr_rcp = airs_rcp_u32(k.nfr, segs);
+	k.spf_rcp = airs_rcp_u32(spf, segs);
 	k.cap = L->cap;
 	k.g = L->encoder_param;
 	k.outlier_param = L->outlier_param;
@@ -1988,6 +1993,9 @@ extern "C" uint32_t airs_dev_encode_stream(struct airs_dev_engine *e, const void
 	k.n = n;
 	k.segs_per_frame = spf;
 	k.num_segs = spf;
+	k.nfr = 1u; // (the front block's divisors, as in the frame launches)
+	k.nfr_rcp = airs_rcp_u32(1u, spf);
+	k.spf_rcp = airs_rcp_u32(spf, spf);
 	k.cap = cap;
 	k.g = encoder_param;
 	k.outlier_param = outlier_param;

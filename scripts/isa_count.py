@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction accounting of one gfx950 kernel (no GPU).
 
-  isa_count.py SYMBOL FILE [--split MNEMONIC ...] [--mnemonics]
+  isa_count.py SYMBOL FILE [--split MNEMONIC ...] [--mnemonics] [--front]
 
 FILE is the assembly of `hipcc -S --cuda-device-only` or a built library
 (libairscmp.so: its gfx950 code objects are disassembled with llvm-objdump).
@@ -19,6 +19,10 @@ The class of an instruction is its mnemonic's prefix and nothing else:
 --split MNEMONIC makes every instruction of that name a region boundary
 beside the barriers (the Rice kernel's packer starts at its one s_setprio);
 --mnemonics adds a histogram of every mnemonic per region.
+--front prints instead the instructions between the kernel's entry and its
+first vector-memory load (global_load_* / buffer_load_* / flat_load_*), in text
+order with their operands, and their counts: the chain a wave walks before its
+first request to memory leaves the CU.
 
 The counts are static: a block inside a loop or behind a branch counts once.
 They say where the instructions are, not how often they issue; the dynamic
@@ -51,7 +55,7 @@ def classify(mnemonic):
 
 
 def asm_kernel(text, sym):
-    """(label or None, mnemonic) in text order, from compiler assembly."""
+    """(label or None, mnemonic, instruction text) in text order, from compiler assembly."""
     lines = text.splitlines()
     try:
         start = next(i for i, ln in enumerate(lines) if ln.startswith(sym + ":"))
@@ -66,9 +70,9 @@ def asm_kernel(text, sym):
             break
         m = re.match(r"^([.\w$]+):$", s)
         if m:
-            out.append((m.group(1), None))
+            out.append((m.group(1), None, None))
         elif not s.startswith("."):
-            out.append((None, s.split()[0]))
+            out.append((None, s.split()[0], " ".join(s.split())))
     return out
 
 
@@ -115,11 +119,11 @@ def lib_kernel(path, sym):
                 continue
             m = re.match(r"^(?:[0-9a-f]+ )?<(L\d+)>:$", s)  # a branch target of --symbolize-operands
             if m:
-                out.append((m.group(1), None))
+                out.append((m.group(1), None, None))
             elif re.match(r"^[0-9a-f]+ <[^>]+>:$", s):  # the next symbol
                 break
             else:
-                out.append((None, s.split()[0]))
+                out.append((None, s.split()[0], " ".join(s.split())))
         return out, {k: meta[k] for k in META_KEYS if k in meta}
     sys.exit(f"{sym}: metadata present, code not found in {path}")
 
@@ -131,6 +135,30 @@ def table(rows, head):
         print(f"{name:<{w}} " + " ".join(f"{cnt[c]:>6}" for c in CLASSES) + f" {sum(cnt.values()):>6}")
 
 
+def is_vmem_load(mn):
+    return mn.startswith(("global_load", "buffer_load", "flat_load"))
+
+
+def front(stream):
+    """The text between the entry and the first vector-memory load."""
+    cnt = collections.Counter()
+    print("\nentry .. first vector-memory load (text order)")
+    for label, mn, text in stream:
+        if label is not None:
+            print(f"{label}:")
+            continue
+        print(f"  {text}")
+        if is_vmem_load(mn):
+            break
+        cnt[mn] += 1
+    else:
+        print("  (no vector-memory load)")
+    print(f"\ninstructions before it: {sum(cnt.values())}")
+    for key, name in (("s_load", "scalar loads"), ("s_waitcnt", "s_waitcnt"), ("v_rcp_iflag_f32", "v_rcp_iflag_f32"),
+                      ("s_mul_hi_u32", "s_mul_hi_u32")):
+        print(f"  {name:<16} {sum(n for m, n in cnt.items() if m.startswith(key))}")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("symbol")
@@ -138,6 +166,8 @@ def main():
     ap.add_argument("--split", action="append", default=[], metavar="MNEMONIC",
                     help="a further region boundary beside s_barrier")
     ap.add_argument("--mnemonics", action="store_true", help="histogram of every mnemonic per region")
+    ap.add_argument("--front", action="store_true",
+                    help="list the instructions from the entry to the first vector-memory load")
     a = ap.parse_args()
     with open(a.file, "rb") as f:
         is_elf = f.read(4) == b"\x7fELF"
@@ -154,12 +184,16 @@ def main():
         if k in meta:
             print(f"  {k[1:]:<28} {meta[k]}")
 
+    if a.front:
+        front(stream)
+        return
+
     regions = [collections.Counter()]
     marks = ["entry"]  # what opens each region
     nbar = 0
     hist = [collections.Counter()]
     blocks = [("(entry)", 0, collections.Counter())]
-    for label, mn in stream:
+    for label, mn, _ in stream:
         if label is not None:
             blocks.append((label, len(regions) - 1, collections.Counter()))
             continue
