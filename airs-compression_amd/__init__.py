@@ -23,6 +23,7 @@ GPU_U16, GPU_I16, GPU_I16_IN_I32 = 0, 1, 2
 GPU_AUTO_RICE = 0x1
 REPORT_DRAWS = 0x8  # CMP_GPU_REPORT_DRAWS
 SEQ_MODEL_IN = 0x1  # CMP_GPU_SEQ_MODEL_IN (cmp_gpu_decompress_sequences)
+STREAM_DECODE_MAX = 536870400  # CMP_GPU_STREAM_DECODE_MAX: bytes cmp_gpu_decode_stream accepts (2^32 - 4096 bits)
 LAYOUT_ROUNDROBIN, LAYOUT_BLOCK, LAYOUT_STREAMS = 0, 1, 2  # enum cmp_gpu_layout
 GATHER_PATCH_IDS = 0x1  # CMP_GPU_GATHER_PATCH_IDS
 OPT_EXCLUSIVE = 1  # cmp_gpu_engine_set_option (include/cmp_gpu.h)
@@ -140,6 +141,9 @@ class AirsLib(CmpLib):
         L.cmp_gpu_encode_stream.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32,
                                             c_uint32, c_void_p, c_uint32, c_void_p]
         L.cmp_gpu_encode_stream.restype = c_uint32
+        L.cmp_gpu_decode_stream.argtypes = [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
+                                            c_uint32, c_void_p, c_void_p]
+        L.cmp_gpu_decode_stream.restype = c_uint32
         L.cmp_gpu_pack_frames.argtypes = [c_void_p, c_void_p, c_uint64, c_uint32, c_void_p, c_uint32, c_void_p,
                                           c_void_p]
         L.cmp_gpu_pack_frames.restype = c_uint32
@@ -245,6 +249,14 @@ class GpuEngine:
         return self.lib.lib.cmp_gpu_encode_stream(self.handle, KIND_TO_GPU[kind], src_ptr, num_samples,
                                                   preprocessing, encoder_type, encoder_param, encoder_outlier,
                                                   dst_ptr, dst_capacity, size_ptr)
+
+    def decode_stream(self, src_ptr: int, src_size: int, num_samples: int, preprocessing: int, encoder_type: int,
+                      encoder_param: int, encoder_outlier: int, dst_ptr: int, status_ptr: int) -> int:
+        """cmp_gpu_decode_stream: the inverse of encode_stream over device pointers (src_size bytes of
+        stream -> num_samples 16-bit samples; *status: num_samples or an error value after synchronize)."""
+        return self.lib.lib.cmp_gpu_decode_stream(self.handle, src_ptr or None, src_size, num_samples, preprocessing,
+                                                  encoder_type, encoder_param, encoder_outlier, dst_ptr or None,
+                                                  status_ptr or None)
 
     def pack_frames(self, frames_ptr: int, frame_stride: int, frame_capacity: int, sizes_ptr: int,
                     num_frames: int, out_ptr: int, offsets_ptr: int) -> int:

@@ -288,6 +288,21 @@ struct airs_decode_seq {
 };
 uint32_t airs_dev_decode_seq(struct airs_dev_engine *e, const struct airs_decode_seq *q);
 
+/* payload-only stream (cmp_gpu_decode_stream, see cmp_gpu.h): the frame
+ * pipeline over one "frame" described by the arguments instead of a header
+ * (no header kernel, no read-back; the parse rounds synchronise), then the end
+ * check: the n-th codeword ends in the stream's last byte and only zero bits
+ * follow.  g and outlier as cmp_coder_resolve leaves them (g = 1 for
+ * UNCOMPRESSED).  src_size at most AIRS_STREAM_DECODE_MAX: every 32-bit bit
+ * position, range end ((s + 1) * 512 of the last subsequence) and parse exit
+ * (at most 48 bits past the end) then stays below 2^32 - 1, the parse's
+ * sentinel.  Scratch: 16 bytes per 512-bit subsequence (a quarter of
+ * src_size, 128 MiB at the limit), 8 per workgroup and 2 per 4096 samples. */
+#define AIRS_STREAM_DECODE_MAX 536870400u /* bytes: 2^32 - 4096 bits */
+uint32_t airs_dev_decode_stream(struct airs_dev_engine *e, const void *src, uint32_t src_size, uint32_t n,
+				uint32_t preprocessing, uint32_t encoder_type, uint32_t g, uint32_t outlier,
+				uint16_t *dst, uint32_t *status);
+
 /* plain memory helpers on the engine stream */
 void *airs_dev_malloc(size_t bytes);
 void airs_dev_free(void *p);

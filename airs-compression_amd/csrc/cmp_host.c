@@ -115,8 +115,10 @@ static uint32_t floor_log2(uint32_t x)
 	return 31u - (uint32_t)__builtin_clz(x);
 }
 
-/* validate (type, g, outlier) and resolve the outlier written to the header */
-static uint32_t coder_resolve(uint32_t type, uint32_t g, uint32_t outlier, uint32_t *resolved)
+/* validate (type, g, outlier) and resolve the outlier written to the header
+ * (declared in cmp_engine.h: cmp_decode_stream.c resolves a stream's encoder
+ * arguments with it) */
+uint32_t cmp_coder_resolve(uint32_t type, uint32_t g, uint32_t outlier, uint32_t *resolved)
 {
 	uint32_t k, cutoff, limit;
 	uint64_t want;
@@ -255,12 +257,12 @@ uint32_t cmp_initialise(struct cmp_context *ctx, const struct cmp_params *params
 		return ERRV(GENERIC);
 	if (params->secondary_iterations >= (1u << CMP_HDR_BITS_SEQUENCE_NUMBER))
 		return ERRV(PARAMS_INVALID);
-	e = coder_resolve(params->primary_encoder_type, params->primary_encoder_param,
+	e = cmp_coder_resolve(params->primary_encoder_type, params->primary_encoder_param,
 			  params->primary_encoder_outlier, NULL);
 	if (is_err(e))
 		return e;
 	if (params->secondary_iterations) {
-		e = coder_resolve(params->secondary_encoder_type, params->secondary_encoder_param,
+		e = cmp_coder_resolve(params->secondary_encoder_type, params->secondary_encoder_param,
 				  params->secondary_encoder_outlier, NULL);
 		if (is_err(e))
 			return e;
@@ -362,7 +364,7 @@ static uint32_t engine_prologue(struct cmp_context *ctx, void *dst, uint32_t cap
 		return ERRV(DST_NULL);
 	if ((uintptr_t)dst & 7u)
 		return ERRV(DST_UNALIGNED);
-	e = coder_resolve(p->enc, p->par, p->outlier_param, &p->outlier);
+	e = cmp_coder_resolve(p->enc, p->par, p->outlier_param, &p->outlier);
 	if (is_err(e))
 		return e;
 	p->hdr_bytes = (p->pre == CMP_PREPROCESS_NONE && p->enc == CMP_ENCODER_UNCOMPRESSED) ? CMP_HDR_SIZE
@@ -666,7 +668,7 @@ uint32_t cmp_gpu_encode_stream(struct cmp_gpu_engine *engine, enum cmp_gpu_sampl
 	if (preprocessing != CMP_PREPROCESS_NONE && preprocessing != CMP_PREPROCESS_DIFF)
 		return ERRV(PARAMS_INVALID);
 	/* the encoder's own checks (encoder.c:185-224) */
-	e = coder_resolve(encoder_type, encoder_param, encoder_outlier, &outlier);
+	e = cmp_coder_resolve(encoder_type, encoder_param, encoder_outlier, &outlier);
 	if (is_err(e))
 		return e;
 	return airs_dev_encode_stream(engine->dev, src, bytes, num_samples, preprocessing, encoder_type,

@@ -23,6 +23,9 @@
 //   scan      per frame, exclusive sum of the workgroups' symbol counts
 //   output    each workgroup decodes its settled ranges again and writes the
 //             residuals; DIFF / MODEL / IWT frames are inverted afterwards.
+// A payload-only stream (airs_dev_decode_stream) is one such frame without a
+// header, described by the caller, with a check that it ends where its last
+// codeword does.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -451,10 +454,12 @@ __global__ __launch_bounds__(1024) void dec_scan_kernel(DecArgs a)
 	}
 }
 
-// residuals (ZigZag undone) into dst; DIFF frames are summed afterwards
-template <bool RICE>
+// residuals (ZigZag undone) into dst; DIFF frames are summed afterwards.
+// STREAM (dec_out_stream_kernel): the lane that decodes sample n - 1 records
+// the bit position after it in *end_pos, for the stream's end check.
+template <bool RICE, bool STREAM = false>
 __device__ __forceinline__ void out_wg(const DecArgs &a, const DecInfo &I, const uint32_t *exits, uint32_t *L,
-				       uint32_t *s_w)
+				       uint32_t *s_w, uint32_t *end_pos = nullptr)
 {
 	const uint32_t f = blockIdx.y, wg = blockIdx.x, t = threadIdx.x, s = wg * DEC_WG + t, lane = t & 63u,
 		       wid = t >> 6;
@@ -494,6 +499,8 @@ __device__ __forceinline__ void out_wg(const DecArgs &a, const DecInfo &I, const
 		if (!len)
 			break;
 		p += len;
+		if (STREAM && j + 1u == I.n) // one lane of the grid: sample j is this codeword
+			*end_pos = p;
 		const uint32_t r = (I.enc == 0u ? m : ((m >> 1) ^ (0u - (m & 1u)))) & 0xFFFFu;
 		if (!vec) {
 			out[j++] = (uint16_t)r;
@@ -533,6 +540,49 @@ __global__ __launch_bounds__(DEC_WG) void dec_out_kernel(DecArgs a, const uint32
 		out_wg<true>(a, I, exits, L, s_w);
 	else
 		out_wg<false>(a, I, exits, L, s_w);
+}
+
+// ---------------------------------------------------------------------
+// Payload-only streams (airs_dev_decode_stream): one "frame" without a
+// header.  Its DecInfo comes from the host as a kernel argument, the output
+// pass records where the n-th codeword ends, and the status step checks that
+// the stream ends there.  The frame paths launch none of these kernels.
+// ---------------------------------------------------------------------
+__global__ void dec_stream_info_kernel(DecArgs a, DecInfo I, uint32_t *end_pos)
+{
+	a.info[0] = I;
+	*end_pos = DEC_BAD; // until the output pass decodes sample n - 1
+}
+
+__global__ __launch_bounds__(DEC_WG) void dec_out_stream_kernel(DecArgs a, const uint32_t *exits, uint32_t *end_pos)
+{
+	__shared__ uint32_t L[DEC_LDSW];
+	__shared__ uint32_t s_w[DEC_WG / 64u];
+	const DecInfo I = a.info[0];
+	if (blockIdx.x * DEC_WG >= I.nsub || I.status) // block-uniform
+		return;
+	if (I.enc == 1u && I.cutoff == I.g)
+		out_wg<true, true>(a, I, exits, L, s_w, end_pos);
+	else
+		out_wg<false, true>(a, I, exits, L, s_w, end_pos);
+}
+
+// The stream is valid only if the n-th codeword ends at bit E within the last
+// of the src_size bytes and the bits after it, the bit writer's flush
+// (bitstream_writer.h:205-227), are zero.  end_pos is still DEC_BAD when the
+// scan found fewer than n codewords (the output pass then did not run).
+__global__ void dec_stream_status_kernel(DecArgs a, const uint32_t *end_pos, uint32_t src_size)
+{
+	const DecInfo I = a.info[0];
+	uint32_t st = I.status;
+	if (!st) {
+		const uint32_t E = *end_pos; // at most nbits + 47 < 2^32 - 8, or DEC_BAD
+		if (E == DEC_BAD || E > I.nbits || (E + 7u) / 8u != src_size)
+			st = ERRV(E_INT_BITSTREAM);
+		else if (E < I.nbits && (a.src[src_size - 1u] & ((1u << (I.nbits - E)) - 1u))) // 1 .. 7 pad bits
+			st = ERRV(E_INT_BITSTREAM);
+	}
+	a.status[0] = st ? st : I.n;
 }
 
 // DIFF (preprocess.c:284-290) inverse: x[i] = x[i-1] + r[i] (int16 wrap), a
@@ -976,10 +1026,15 @@ using namespace airsdec;
 // sequences of fpc: MODEL frames are taken without a model, dec_model_kernel
 // gives way to the plan and the chain, which write the statuses, and the
 // checksums are verified when asked for.  No further synchronisation.
+//
+// With a stream description (airs_dev_decode_stream) there is one "frame" of
+// src_cap bytes without a header: its DecInfo is the caller's, so the header
+// kernel and its read-back are skipped, the output pass records where the
+// last codeword ends, and the status step checks the stream's end.
 static uint32_t decode_frames(struct airs_dev_engine *e, const void *src, uint64_t src_stride, uint32_t src_cap,
 			      uint32_t num_frames, uint16_t *dst, uint64_t dst_stride, uint32_t dst_samples,
 			      uint32_t *status, const uint16_t *model, uint64_t model_stride,
-			      const struct airs_decode_seq *seq)
+			      const struct airs_decode_seq *seq, const DecInfo *stream = nullptr)
 {
 	if (!e || !src || !dst || !status || !num_frames || (src_stride & 7u) || ((uintptr_t)src & 7u) ||
 	    ((uintptr_t)dst & 1u) || (dst_stride & 1u))
@@ -1007,12 +1062,18 @@ static uint32_t decode_frames(struct airs_dev_engine *e, const void *src, uint64
 	a.info = (DecInfo *)hdr;
 	a.maxsub = (uint32_t *)(hdr + info_bytes);
 	a.changed = a.maxsub + 1;
-	DCHECK(hipMemsetAsync(a.maxsub, 0, 16, s));
-	hipLaunchKernelGGL(dec_hdr_kernel, dim3((num_frames + 255u) / 256u), dim3(256), 0, s, a);
 	// largest subsequence count, (changed), any IWT frame, largest frame with a checksum (sequences)
 	uint32_t hv[4] = {0, 0, 0, 0};
-	DCHECK(hipMemcpyAsync(hv, a.maxsub, 16, hipMemcpyDeviceToHost, s));
-	DCHECK(hipStreamSynchronize(s));
+	uint32_t *end_pos = a.maxsub + 2; // streams: where the last codeword ends (no IWT flag there)
+	if (stream) {
+		hipLaunchKernelGGL(dec_stream_info_kernel, dim3(1), dim3(1), 0, s, a, *stream, end_pos);
+		hv[0] = stream->nsub; // follows from src_size: nothing to read back
+	} else {
+		DCHECK(hipMemsetAsync(a.maxsub, 0, 16, s));
+		hipLaunchKernelGGL(dec_hdr_kernel, dim3((num_frames + 255u) / 256u), dim3(256), 0, s, a);
+		DCHECK(hipMemcpyAsync(hv, a.maxsub, 16, hipMemcpyDeviceToHost, s));
+		DCHECK(hipStreamSynchronize(s));
+	}
 	const uint32_t msub = hv[0];
 	const bool any_iwt = hv[2] != 0u;
 	a.msub = msub ? msub : 1u;
@@ -1053,8 +1114,20 @@ static uint32_t decode_frames(struct airs_dev_engine *e, const void *src, uint64
 				break;
 		}
 		hipLaunchKernelGGL(dec_scan_kernel, dim3(num_frames), dim3(1024), 0, s, a);
-		hipLaunchKernelGGL(dec_out_kernel, grid, dim3(DEC_WG), 0, s, a, (const uint32_t *)ein);
 		const dim3 tg(tiles, num_frames);
+		if (stream) {
+			hipLaunchKernelGGL(dec_out_stream_kernel, grid, dim3(DEC_WG), 0, s, a, (const uint32_t *)ein, end_pos);
+			if (stream->pre == 1u) {
+				hipLaunchKernelGGL(dec_tile_sum_kernel, tg, dim3(256), 0, s, a, tiles);
+				hipLaunchKernelGGL(dec_tile_prefix_kernel, dim3(1), dim3(1024), 0, s, a, tiles);
+				hipLaunchKernelGGL(dec_tile_scan_kernel, tg, dim3(256), 0, s, a, tiles);
+			}
+			hipLaunchKernelGGL(dec_stream_status_kernel, dim3(1), dim3(1), 0, s, a, (const uint32_t *)end_pos,
+					   src_cap);
+			DCHECK(hipGetLastError());
+			return 0;
+		}
+		hipLaunchKernelGGL(dec_out_kernel, grid, dim3(DEC_WG), 0, s, a, (const uint32_t *)ein);
 		hipLaunchKernelGGL(dec_tile_sum_kernel, tg, dim3(256), 0, s, a, tiles);
 		hipLaunchKernelGGL(dec_tile_prefix_kernel, dim3(num_frames), dim3(1024), 0, s, a, tiles);
 		hipLaunchKernelGGL(dec_tile_scan_kernel, tg, dim3(256), 0, s, a, tiles);
@@ -1131,6 +1204,32 @@ extern "C" uint32_t airs_dev_decode(struct airs_dev_engine *e, const void *src, 
 {
 	return decode_frames(e, src, src_stride, src_cap, num_frames, dst, dst_stride, dst_samples, status, model,
 			     model_stride, nullptr);
+}
+
+// The stream as one frame: what dec_hdr_kernel would take from a header.
+// nbits <= 2^32 - 4096, so nsub * DEC_B <= nbits + 511 and every exit
+// (<= nbits + 47) stay below DEC_BAD without a wrap.
+extern "C" uint32_t airs_dev_decode_stream(struct airs_dev_engine *e, const void *src, uint32_t src_size, uint32_t n,
+					  uint32_t preprocessing, uint32_t encoder_type, uint32_t g, uint32_t outlier,
+					  uint16_t *dst, uint32_t *status)
+{
+	if (!n || n > AIRS_STREAM_MAX || !src_size || src_size > AIRS_STREAM_DECODE_MAX || preprocessing > 1u ||
+	    encoder_type > 2u || !g || g > 0xFFFFu)
+		return ERRV(E_GENERIC);
+	DecInfo I;
+	memset(&I, 0, sizeof(I));
+	I.n = n;
+	I.nbits = 8u * src_size;
+	I.hdr_bits = 0;
+	I.enc = encoder_type;
+	I.pre = preprocessing;
+	I.g = g;
+	I.k = 31u - (uint32_t)__builtin_clz(g);
+	I.cutoff = (2u << I.k) - g;
+	I.outlier = outlier;
+	I.nsub = (I.nbits + DEC_B - 1u) / DEC_B;
+	I.wmax = (src_size + 3u) / 4u - 1u;
+	return decode_frames(e, src, 0, src_size, 1, dst, 0, n, status, nullptr, 0, nullptr, &I);
 }
 
 extern "C" uint32_t airs_dev_decode_seq(struct airs_dev_engine *e, const struct airs_decode_seq *q)

@@ -236,6 +236,60 @@ uint32_t cmp_gpu_encode_stream(struct cmp_gpu_engine *engine, enum cmp_gpu_sampl
 			       void *dst, uint32_t dst_capacity, uint32_t *size);
 
 /*
+ * The inverse of cmp_gpu_encode_stream: the src_size bytes at src (device,
+ * 8-byte aligned, readable up to src_size rounded up to 4) as *size reported
+ * them, decoded into num_samples 16-bit samples at dst (device, 2-byte
+ * aligned; 16 is fastest): the low halves for a stream encoded from
+ * i16-in-i32, as with the frame decoder, so there is no type argument.
+ * preprocessing, encoder_type, encoder_param and encoder_outlier mean exactly
+ * what they meant to the encoder and are resolved by the same checks.  A
+ * stream has no header, so nothing declares its payload size; the caller does,
+ * and the decoder verifies it.  With E the bit position where the
+ * num_samples-th codeword ends, a stream is valid only if num_samples valid
+ * codewords exist, E <= 8 * src_size, (E + 7) / 8 == src_size, and the bits
+ * [E, 8 * src_size) are zero (the bit writer's flush,
+ * lib/common/bitstream_writer.h:205-227).  Anything else -- too few codewords,
+ * an invalid one, E past the end, bytes left over, pad bits set: a wrong count,
+ * a wrong size or wrong parameters -- is CMP_ERR_INT_BITSTREAM.  An
+ * UNCOMPRESSED stream therefore needs src_size == 2 * num_samples.
+ *
+ * *status (device) receives num_samples or that error value; it is valid after
+ * cmp_gpu_synchronize.  The result never depends on bytes past src_size, and
+ * nothing is written past dst[num_samples - 1] (after an error the samples
+ * before it are unspecified).
+ *
+ * Returns CMP_ERR_NO_ERROR or a call-level refusal, before anything reaches the
+ * device, checked in this order: NULL engine or status CMP_ERR_GENERIC; NULL
+ * src CMP_ERR_SRC_NULL; src not 8-byte aligned CMP_ERR_GENERIC; NULL dst
+ * CMP_ERR_DST_NULL; odd dst CMP_ERR_DST_UNALIGNED; num_samples 0 or above
+ * 89478485, or src_size 0 or above CMP_GPU_STREAM_DECODE_MAX,
+ * CMP_ERR_SRC_SIZE_WRONG; preprocessing other than NONE / DIFF
+ * CMP_ERR_PARAMS_INVALID; encoder arguments the encoder's own checks refuse:
+ * the error those checks return.
+ *
+ * CMP_GPU_STREAM_DECODE_MAX is 2^32 - 4096 bits.  The decoder keeps bit
+ * positions in 32 bits: below that size every position, every range end (a
+ * multiple of 512 bits at or past the end) and every parse exit (up to 48 bits
+ * past the end) stays clear of the 32-bit wrap and of the parse's sentinel
+ * 0xFFFFFFFF.  Any stream of at most 89478400 samples fits (48 bits per
+ * sample at most); that is 85 samples below the encoder's limit of 89478485,
+ * whose worst case is 510 bytes larger.  A stream of 89478401 to 89478485
+ * samples decodes as long as its size is within the limit, which all but
+ * pathological inputs are.
+ *
+ * Synchronises with the host for the parse rounds only (the stream is cut into
+ * 512-bit subsequences whose count follows from src_size; rounds repeat until
+ * the parse settles); the remaining launches stay queued on the engine's
+ * stream.  Engine scratch: about 16 bytes per subsequence, a quarter of
+ * src_size (128 MiB at the limit).  Build-defined extension.
+ */
+#define CMP_GPU_STREAM_DECODE_MAX 536870400u /* bytes */
+uint32_t cmp_gpu_decode_stream(struct cmp_gpu_engine *engine, const void *src, uint32_t src_size,
+			       uint32_t num_samples, enum cmp_preprocessing preprocessing,
+			       enum cmp_encoder_type encoder_type, uint32_t encoder_param, uint32_t encoder_outlier,
+			       uint16_t *dst, uint32_t *status);
+
+/*
  * Pack the frames of a strided batch output (frame f at frames + f*frame_stride,
  * sizes[f] bytes, as cmp_gpu_compress leaves them) back to back into out: frame
  * f at out + offsets[f], offsets 8-byte aligned, offsets[num_frames] = the
