@@ -307,11 +307,15 @@ struct frame_io {
 struct pass {
 	uint32_t pre, enc, par, outlier_param, outlier;
 	uint32_t model_mode;
-	uint32_t seq;
 	uint32_t hdr_bytes;
+	uint8_t seq; /* a byte, as in the context and the header (walk_upload reads it at a stride) */
 };
 
 enum { SLOT_SRC = 0, SLOT_DST, SLOT_MODEL, SLOT_STATUS, SLOT_CK, SLOT_IDS, SLOT_G, SLOT_AUX, SLOT_FL, SLOT_SIZES, SLOT_MSAVE };
+/* a one-launch batch path's answer when it does not apply (nothing launched):
+ * neither 0 nor an error value */
+#define WALK_NO 1u
+#define IWT_SCRATCH_MAX (1ull << 30) /* device scratch batch_iwt may take for coefficients */
 
 /* The host-pointer API stages every frame through one process-wide engine
  * (device scratch slots, look-back state).  Calls on different contexts may
@@ -1099,6 +1103,61 @@ static uint32_t first_cap(const struct cmp_context *ctx, const struct cmp_gpu_ba
 	return ctx->params.uncompressed_fallback_enabled && b->dst_capacity >= raw ? raw : b->dst_capacity;
 }
 
+/* Draw the identifiers of a batch in the reference's call order
+ * (context-major): frame f draws draws[f] identifiers and carries the last
+ * one; a frame without a draw carries its context's, which is
+ * from[c].identifier at the context's first frame.  report (optional)
+ * receives the draw counts. */
+static void draw_identifiers(const struct cmp_context *from, uint32_t num_ctx, uint32_t fpc, const uint8_t *draws,
+			     uint64_t *ids, uint8_t *report)
+{
+	uint32_t c, a, k;
+
+	for (c = 0; c < num_ctx; c++) {
+		uint64_t id = from[c].identifier;
+
+		for (a = 0; a < fpc; a++) {
+			const uint32_t f = c * fpc + a;
+
+			for (k = 0; k < draws[f]; k++)
+				id = next_identifier();
+			ids[f] = id;
+			if (report)
+				report[f] = draws[f];
+		}
+	}
+}
+
+/* One work-buffer pointer per context into SLOT_AUX (*d_ptr).  The copy is
+ * asynchronous: the caller frees the staging array *host once the stream is
+ * synchronised. */
+static uint32_t upload_work_ptrs(struct airs_dev_engine *dev, const struct cmp_context *ctx, uint32_t num_ctx,
+				 uint64_t **d_ptr, uint64_t **host)
+{
+	uint64_t *hp = malloc((size_t)num_ctx * 8u);
+	uint32_t c;
+
+	*host = hp;
+	*d_ptr = airs_dev_scratch(dev, SLOT_AUX, (size_t)num_ctx * 8u);
+	if (!hp || !*d_ptr)
+		return ERRV(GENERIC);
+	for (c = 0; c < num_ctx; c++)
+		hp[c] = (uint64_t)(uintptr_t)ctx[c].work_buf;
+	return airs_dev_h2d(dev, *d_ptr, hp, (size_t)num_ctx * 8u);
+}
+
+/* checksums of all frames of the batch into SLOT_CK (*d_ck) */
+static uint32_t batch_checksums(struct airs_dev_engine *dev, const struct cmp_gpu_batch *b, uint32_t total,
+				uint32_t **d_ck)
+{
+	const uint32_t bytes = b->type == CMP_GPU_I16_IN_I32 ? 4u : 2u;
+
+	*d_ck = airs_dev_scratch(dev, SLOT_CK, (size_t)total * 4u);
+	if (!*d_ck)
+		return ERRV(GENERIC);
+	return airs_dev_checksum(dev, b->src, b->src_stride, bytes, b->src_size / bytes, total, NULL, *d_ck);
+}
+
 /* can batch_device_exact() run this batch?  pp / ps receive the two passes */
 static int device_exact_ok(const struct cmp_context *ctx, uint32_t num_ctx, const struct cmp_gpu_batch *b,
 			   uint32_t n, struct pass *pp, struct pass *ps)
@@ -1204,27 +1263,18 @@ static uint32_t batch_device_exact(struct cmp_gpu_engine *eng, struct cmp_contex
 			S.model = mbase;
 			S.model_stride = mstride;
 		} else {
-			uint64_t *hp = calloc(num_ctx, sizeof(uint64_t));
+			uint64_t *hp;
 
-			d_ptr = airs_dev_scratch(dev, SLOT_AUX, (size_t)num_ctx * 8u);
-			if (!hp || !d_ptr) {
-				free(hp);
-				e = ERRV(GENERIC);
-			} else {
-				for (c = 0; c < num_ctx; c++)
-					hp[c] = (uint64_t)(uintptr_t)ctx[c].work_buf;
-				e = airs_dev_h2d(dev, d_ptr, hp, (size_t)num_ctx * 8u);
-				if (!is_err(e))
-					e = airs_dev_sync(dev);
-				free(hp);
-				S.model_ptrs = d_ptr;
-			}
+			e = upload_work_ptrs(dev, ctx, num_ctx, &d_ptr, &hp);
+			if (!is_err(e))
+				e = airs_dev_sync(dev);
+			free(hp);
+			S.model_ptrs = d_ptr;
 		}
 		mal16 = al;
 	}
 	if (!is_err(e) && P->checksum_enabled) {
-		d_ck = airs_dev_scratch(dev, SLOT_CK, (size_t)total * 4u);
-		e = d_ck ? airs_dev_checksum(dev, b->src, b->src_stride, bytes, n, total, NULL, d_ck) : ERRV(GENERIC);
+		e = batch_checksums(dev, b, total, &d_ck);
 		S.checksums = d_ck;
 	}
 	if (!is_err(e) && (b->flags & CMP_GPU_AUTO_RICE)) {
@@ -1290,19 +1340,9 @@ static uint32_t batch_device_exact(struct cmp_gpu_engine *eng, struct cmp_contex
 		e = airs_dev_sync(dev);
 	if (is_err(e))
 		goto out;
+	draw_identifiers(ctx, num_ctx, fpc, host_draws, ids, REPORT_DRAWS(b) ? b->draws : NULL);
 	for (c = 0; c < num_ctx; c++) {
-		uint64_t id = ctx[c].identifier;
-
-		for (a = 0; a < fpc; a++) {
-			const uint32_t f = c * fpc + a;
-
-			for (uint32_t k = 0; k < host_draws[f]; k++)
-				id = next_identifier();
-			ids[f] = id;
-			if (REPORT_DRAWS(b))
-				b->draws[f] = host_draws[f];
-		}
-		ctx[c].identifier = id;
+		ctx[c].identifier = ids[c * fpc + fpc - 1u];
 		ctx[c].sequence_number = (uint8_t)host_state[2u * c];
 		ctx[c].model_size = host_state[2u * c + 1u];
 	}
@@ -1323,162 +1363,219 @@ out:
 }
 
 /*
- * MODEL contexts in one launch (airs_dev_walk, enc_walk.hip): every frame of
- * the batch, acquisition after acquisition, with each context's model kept on
- * the chip.  Used in the asynchronous mode (no frame can fail or fall back)
- * when every context has the same parameters with a MODEL secondary pass and
- * the plan the host replayed is the one the walk's pass rule gives.
- * Returns 0, an error value, or WALK_NO (not applicable; nothing launched).
+ * The three MODEL batch paths below hand the whole batch to airs_dev_walk
+ * (enc_walk.hip): every frame, acquisition after acquisition, with each
+ * context's model kept on the chip.  walk_prepare() decides what they share:
+ * whether a walk applies at all, and the launch as far as the batch and the
+ * contexts' parameters give it.
  */
-#define WALK_NO 1u
-static uint32_t batch_walk(struct cmp_gpu_engine *eng, const struct cmp_context *ctx, uint32_t num_ctx, uint32_t fpc,
-			   const struct cmp_gpu_batch *b, const struct frame_plan *plan)
+struct walk_prep {
+	struct airs_walk w;   /* the caller adds cap and what else is its own */
+	uint32_t n, total;    /* samples of a frame, frames of the batch */
+	uint32_t raw;         /* the raw (fallback) frame's size */
+	uint32_t m_strided;   /* models at w.model + c * w.model_stride; else a pointer list (walk_upload) */
+	uint32_t seq_same;    /* every context at ctx[0]'s sequence number (w.seq0) */
+};
+
+/* Returns 0 or WALK_NO; allocates and launches nothing.  A walk applies when
+ * every context has the same parameters with a MODEL secondary pass and a
+ * NONE/DIFF primary pass coded with the configured parameters, and the models
+ * are strided or 16-byte aligned.  need_fb: the batch is in exact mode and the
+ * uncompressed fallback must be the only way a frame's outcome can change the
+ * next frame's pass: the fallback enabled with dst_capacity >= the raw frame
+ * size (the first attempt's capacity is then the raw size, so a frame either
+ * fits or falls back), and no secondary first frame whose model size differs
+ * (no SRC_SIZE_MISMATCH). */
+static uint32_t walk_prepare(const struct cmp_context *ctx, uint32_t num_ctx, uint32_t fpc,
+			     const struct cmp_gpu_batch *b, int need_fb, struct walk_prep *pr)
 {
-	struct airs_dev_engine *dev = eng->dev;
 	const struct cmp_params *P = &ctx[0].params;
 	const uint32_t bytes = b->type == CMP_GPU_I16_IN_I32 ? 4u : 2u;
-	const uint32_t n = b->src_size / bytes, total = num_ctx * fpc;
-	const uint64_t worst = frame_worst(n);
-	struct airs_walk w;
-	uint32_t c, a, e, seq_same = 1, id_aff = 1, m_strided = 1;
+	const uint32_t n = b->src_size / bytes, raw = raw_frame_size(&ctx[0], n);
+	struct airs_walk *w = &pr->w;
 	uint64_t mbase, mstep;
+	uint32_t c;
 
 	if (!model_needed(P) || (P->primary_preprocessing != CMP_PREPROCESS_NONE &&
 				 P->primary_preprocessing != CMP_PREPROCESS_DIFF))
 		return WALK_NO;
+	if (need_fb && (!P->uncompressed_fallback_enabled || b->dst_capacity < raw || raw > 0xFFFFFFu))
+		return WALK_NO;
 	/* the walk codes with the configured parameters (AUTO_RICE: per-step launches) */
 	if ((b->flags & CMP_GPU_AUTO_RICE) && P->primary_encoder_type == CMP_ENCODER_GOLOMB_ZERO)
 		return WALK_NO;
-	for (c = 0; c < num_ctx; c++)
+	memset(pr, 0, sizeof(*pr));
+	pr->n = n;
+	pr->total = num_ctx * fpc;
+	pr->raw = raw;
+	pr->seq_same = 1;
+	for (c = 0; c < num_ctx; c++) {
+		const uint32_t sq = ctx[c].sequence_number;
+
 		if (!same_params(&ctx[c].params, P))
 			return WALK_NO;
-	memset(&w, 0, sizeof(w));
-	w.src = b->src;
-	w.src_stride = b->src_stride;
-	w.sample_bytes = bytes;
-	w.is_unsigned = b->type == CMP_GPU_U16;
-	w.n = n;
-	w.num_ctx = num_ctx;
-	w.fpc = fpc;
-	w.dst = b->dst;
-	w.dst_stride = b->dst_stride;
-	w.cap = (uint64_t)b->dst_capacity < worst ? b->dst_capacity : (uint32_t)worst;
-	w.pre_p = P->primary_preprocessing;
-	w.enc_p = P->primary_encoder_type;
-	w.g_p = P->primary_encoder_param;
-	w.outl_p = P->primary_encoder_outlier;
-	w.enc_s = P->secondary_encoder_type;
-	w.g_s = P->secondary_encoder_param;
-	w.outl_s = P->secondary_encoder_outlier;
-	w.model_rate = P->model_rate;
-	w.iters = P->secondary_iterations;
-	w.checksum_enabled = P->checksum_enabled ? 1u : 0u;
-	w.status = b->sizes;
+		if (need_fb && sq != 0u && sq <= P->secondary_iterations && ctx[c].model_size != 2u * n)
+			return WALK_NO; /* the reference returns SRC_SIZE_MISMATCH for that frame */
+		if (sq != ctx[0].sequence_number)
+			pr->seq_same = 0;
+	}
+	w->src = b->src;
+	w->src_stride = b->src_stride;
+	w->sample_bytes = bytes;
+	w->is_unsigned = b->type == CMP_GPU_U16;
+	w->n = n;
+	w->num_ctx = num_ctx;
+	w->fpc = fpc;
+	w->dst = b->dst;
+	w->dst_stride = b->dst_stride;
+	w->pre_p = P->primary_preprocessing;
+	w->enc_p = P->primary_encoder_type;
+	w->g_p = P->primary_encoder_param;
+	w->outl_p = P->primary_encoder_outlier;
+	w->enc_s = P->secondary_encoder_type;
+	w->g_s = P->secondary_encoder_param;
+	w->outl_s = P->secondary_encoder_outlier;
+	w->model_rate = P->model_rate;
+	w->iters = P->secondary_iterations;
+	w->checksum_enabled = P->checksum_enabled ? 1u : 0u;
+	w->status = b->sizes;
+	w->seq0 = ctx[0].sequence_number;
+	/* model of context c: strided work buffers, or a pointer list */
+	mbase = (uint64_t)(uintptr_t)ctx[0].work_buf;
+	mstep = num_ctx > 1 ? (uint64_t)(uintptr_t)ctx[1].work_buf - mbase : 0;
+	pr->m_strided = 1;
+	for (c = 0; c < num_ctx && pr->m_strided; c++)
+		pr->m_strided = (uint64_t)(uintptr_t)ctx[c].work_buf == mbase + c * mstep;
+	if (!pr->m_strided)
+		for (c = 0; c < num_ctx; c++)
+			if ((uintptr_t)ctx[c].work_buf & 15u)
+				return WALK_NO;
+	w->model = (void *)(uintptr_t)mbase;
+	w->model_stride = pr->m_strided ? mstep : 0;
+	return 0;
+}
+
+/* can the device run the prepared walk?  Asked once the caller has set its
+ * own fields; the pointer list is not uploaded yet (walk_prepare checked its
+ * alignment), so it goes in without a model */
+static int walk_supported(const struct walk_prep *pr)
+{
+	struct airs_walk chk = pr->w;
+
+	if (!pr->m_strided)
+		chk.model = NULL, chk.model_stride = 0;
+	return airs_dev_walk_supported(&chk);
+}
+
+/* Device copies of what a walk cannot address by a rule: the work-buffer
+ * pointers where the models are not strided, the identifiers where the caller
+ * passes a list, and the contexts' first sequence numbers where they differ
+ * (the byte at seq0 + c * step, into d_seq: device scratch of the caller's
+ * choice).  One synchronise, then the host staging is freed; nothing is done
+ * for strided models at one sequence number with affine identifiers. */
+static uint32_t walk_upload(struct airs_dev_engine *dev, struct walk_prep *pr, const struct cmp_context *ctx,
+			    const uint8_t *seq0, size_t step, uint8_t *d_seq, const uint64_t *ids)
+{
+	struct airs_walk *w = &pr->w;
+	uint64_t *d_ptr = NULL, *h_ptr = NULL;
+	uint8_t *h_seq = NULL;
+	uint32_t c, e = 0;
+
+	if (pr->m_strided && pr->seq_same && !ids)
+		return 0;
+	if (!pr->m_strided) {
+		e = upload_work_ptrs(dev, ctx, w->num_ctx, &d_ptr, &h_ptr);
+		w->model_ptrs = d_ptr;
+	}
+	if (ids && !is_err(e)) {
+		uint64_t *d_ids = airs_dev_scratch(dev, SLOT_IDS, (size_t)pr->total * 8u);
+
+		e = d_ids ? airs_dev_h2d(dev, d_ids, ids, (size_t)pr->total * 8u) : ERRV(GENERIC);
+		w->ids = d_ids;
+	}
+	if (!pr->seq_same && !is_err(e)) {
+		h_seq = malloc(w->num_ctx);
+		if (!h_seq || !d_seq)
+			e = ERRV(GENERIC);
+		for (c = 0; c < w->num_ctx && !is_err(e); c++)
+			h_seq[c] = seq0[c * step];
+		if (!is_err(e))
+			e = airs_dev_h2d(dev, d_seq, h_seq, w->num_ctx);
+		w->seq0s = d_seq;
+	}
+	if (!is_err(e))
+		e = airs_dev_sync(dev);
+	free(h_ptr);
+	free(h_seq);
+	return e;
+}
+
+/*
+ * The walk in the asynchronous mode (no frame can fail or fall back): applies
+ * when the plan the host replayed is the one the walk's pass rule gives.  ids:
+ * host scratch for total identifiers.
+ * Returns 0, an error value, or WALK_NO (not applicable; nothing launched).
+ */
+static uint32_t batch_walk(struct cmp_gpu_engine *eng, const struct cmp_context *ctx, uint32_t num_ctx, uint32_t fpc,
+			   const struct cmp_gpu_batch *b, const struct frame_plan *plan, uint64_t *ids)
+{
+	struct airs_dev_engine *dev = eng->dev;
+	struct walk_prep pr;
+	struct airs_walk *w = &pr.w;
+	uint32_t c, a, e, id_aff = 1, *d_ck;
+	uint8_t *d_seq = NULL;
+	uint64_t worst;
+
+	if (walk_prepare(ctx, num_ctx, fpc, b, 0, &pr))
+		return WALK_NO;
+	worst = frame_worst(pr.n);
+	w->cap = (uint64_t)b->dst_capacity < worst ? b->dst_capacity : (uint32_t)worst;
 	/* the walk's pass rule (cmp.c:228-248), started from each context's
-	 * first frame, must give the replayed plan frame by frame */
+	 * first frame, must give the replayed plan frame by frame (the replay
+	 * has advanced the contexts: the sequence numbers are the plan's) */
+	pr.seq_same = 1;
 	for (c = 0; c < num_ctx; c++) {
 		uint32_t sq = plan[c * fpc].p.seq;
 
 		if (sq != plan[0].p.seq)
-			seq_same = 0;
+			pr.seq_same = 0;
 		for (a = 0; a < fpc; a++) {
 			const struct pass *p = &plan[c * fpc + a].p;
-			const int prim = sq == 0 || sq > w.iters;
+			const int prim = sq == 0 || sq > w->iters;
 
 			if (p->seq != (prim ? 0u : sq) ||
-			    p->pre != (prim ? w.pre_p : (uint32_t)CMP_PREPROCESS_MODEL) ||
-			    p->enc != (prim ? w.enc_p : w.enc_s) || p->par != (prim ? w.g_p : w.g_s) ||
+			    p->pre != (prim ? w->pre_p : (uint32_t)CMP_PREPROCESS_MODEL) ||
+			    p->enc != (prim ? w->enc_p : w->enc_s) || p->par != (prim ? w->g_p : w->g_s) ||
 			    p->model_mode != (prim ? (uint32_t)AIRS_MODEL_STORE : (uint32_t)AIRS_MODEL_UPDATE))
 				return WALK_NO;
 			sq = prim ? 1u : sq + 1u;
 		}
 	}
-	w.seq0 = plan[0].p.seq;
-	/* model of context c: strided work buffers, or a pointer list */
-	mbase = (uint64_t)(uintptr_t)ctx[0].work_buf;
-	mstep = num_ctx > 1 ? (uint64_t)(uintptr_t)ctx[1].work_buf - mbase : 0;
-	for (c = 0; c < num_ctx && m_strided; c++)
-		m_strided = (uint64_t)(uintptr_t)ctx[c].work_buf == mbase + c * mstep;
-	if (!m_strided)
-		for (c = 0; c < num_ctx; c++)
-			if ((uintptr_t)ctx[c].work_buf & 15u)
-				return WALK_NO;
-	w.model = (void *)(uintptr_t)mbase;
-	w.model_stride = m_strided ? mstep : 0;
+	w->seq0 = plan[0].p.seq;
 	/* identifiers: base + c cstep + a astep, or a list */
-	w.id_base = plan[0].id;
-	w.id_cstep = num_ctx > 1 ? plan[fpc].id - plan[0].id : 0;
-	w.id_astep = fpc > 1 ? plan[1].id - plan[0].id : 0;
+	w->id_base = plan[0].id;
+	w->id_cstep = num_ctx > 1 ? plan[fpc].id - plan[0].id : 0;
+	w->id_astep = fpc > 1 ? plan[1].id - plan[0].id : 0;
 	for (c = 0; c < num_ctx && id_aff; c++)
 		for (a = 0; a < fpc && id_aff; a++)
-			id_aff = plan[c * fpc + a].id == w.id_base + c * w.id_cstep + a * w.id_astep;
-	{
-		struct airs_walk chk = w;
-
-		if (!m_strided) /* the pointer list is checked for alignment above */
-			chk.model = NULL, chk.model_stride = 0;
-		if (!airs_dev_walk_supported(&chk))
-			return WALK_NO;
-	}
-	/* device copies of what is not affine; the stream is synchronised before
-	 * the host arrays are freed */
-	if (!m_strided || !id_aff || !seq_same) {
-		uint64_t *d_ptr = NULL, *d_ids = NULL, *h_ptr = NULL, *h_ids = NULL;
-		uint8_t *d_seq = NULL, *h_seq = NULL;
-
-		e = 0;
-		if (!m_strided) {
-			h_ptr = malloc((size_t)num_ctx * 8u);
-			d_ptr = airs_dev_scratch(dev, SLOT_AUX, (size_t)num_ctx * 8u);
-			if (!h_ptr || !d_ptr)
-				e = ERRV(GENERIC);
-			for (c = 0; c < num_ctx && !is_err(e); c++)
-				h_ptr[c] = (uint64_t)(uintptr_t)ctx[c].work_buf;
-			if (!is_err(e))
-				e = airs_dev_h2d(dev, d_ptr, h_ptr, (size_t)num_ctx * 8u);
-			w.model_ptrs = d_ptr;
-		}
-		if (!id_aff && !is_err(e)) {
-			h_ids = malloc((size_t)total * 8u);
-			d_ids = airs_dev_scratch(dev, SLOT_IDS, (size_t)total * 8u);
-			if (!h_ids || !d_ids)
-				e = ERRV(GENERIC);
-			for (c = 0; c < total && !is_err(e); c++)
-				h_ids[c] = plan[c].id;
-			if (!is_err(e))
-				e = airs_dev_h2d(dev, d_ids, h_ids, (size_t)total * 8u);
-			w.ids = d_ids;
-		}
-		if (!seq_same && !is_err(e)) {
-			h_seq = malloc(num_ctx);
-			d_seq = airs_dev_scratch(dev, SLOT_FL, num_ctx);
-			if (!h_seq || !d_seq)
-				e = ERRV(GENERIC);
-			for (c = 0; c < num_ctx && !is_err(e); c++)
-				h_seq[c] = (uint8_t)plan[c * fpc].p.seq;
-			if (!is_err(e))
-				e = airs_dev_h2d(dev, d_seq, h_seq, num_ctx);
-			w.seq0s = d_seq;
-		}
-		if (!is_err(e))
-			e = airs_dev_sync(dev);
-		free(h_ptr);
-		free(h_ids);
-		free(h_seq);
+			id_aff = plan[c * fpc + a].id == w->id_base + c * w->id_cstep + a * w->id_astep;
+	if (!walk_supported(&pr))
+		return WALK_NO;
+	if (!id_aff)
+		for (c = 0; c < pr.total; c++)
+			ids[c] = plan[c].id;
+	if (!pr.seq_same)
+		d_seq = airs_dev_scratch(dev, SLOT_FL, num_ctx);
+	e = walk_upload(dev, &pr, ctx, &plan[0].p.seq, fpc * sizeof(*plan), d_seq, id_aff ? NULL : ids);
+	if (is_err(e))
+		return e;
+	if (w->checksum_enabled) {
+		e = batch_checksums(dev, b, pr.total, &d_ck);
 		if (is_err(e))
 			return e;
+		w->checksums = d_ck;
 	}
-	if (P->checksum_enabled) {
-		uint32_t *d_ck = airs_dev_scratch(dev, SLOT_CK, (size_t)total * 4u);
-
-		if (!d_ck)
-			return ERRV(GENERIC);
-		e = airs_dev_checksum(dev, b->src, b->src_stride, bytes, n, total, NULL, d_ck);
-		if (is_err(e))
-			return e;
-		w.checksums = d_ck;
-	}
-	return airs_dev_walk(dev, &w);
+	return airs_dev_walk(dev, w);
 }
 
 /*
@@ -1487,187 +1584,80 @@ static uint32_t batch_walk(struct cmp_gpu_engine *eng, const struct cmp_context 
  * (cmp.c:342-393) and reports every frame's identifier draws and each
  * context's final sequence number; one read-back, then the identifiers are
  * drawn in call order and patched into the headers, as batch_device_exact
- * does.  Applies when the fallback is the only way a frame's outcome can
- * change the next frame's pass: every context with the same parameters, the
- * fallback enabled and dst_capacity >= the raw frame size (the first
- * attempt's capacity is then the raw size, so a frame either fits or falls
- * back), and no secondary first frame whose model size differs (no
- * SRC_SIZE_MISMATCH).  Returns 0, an error value, or WALK_NO.
+ * does.  Returns 0, an error value, or WALK_NO.
  */
 static uint32_t batch_walk_fb(struct cmp_gpu_engine *eng, struct cmp_context *ctx, uint32_t num_ctx, uint32_t fpc,
 			      const struct cmp_gpu_batch *b, uint64_t *ids)
 {
 	struct airs_dev_engine *dev = eng->dev;
-	const struct cmp_params *P = &ctx[0].params;
-	const uint32_t bytes = b->type == CMP_GPU_I16_IN_I32 ? 4u : 2u;
-	const uint32_t n = b->src_size / bytes, total = num_ctx * fpc;
-	const uint32_t raw = raw_frame_size(&ctx[0], n);
-	const size_t tb = ((size_t)total + 15u) & ~(size_t)15u;
-	struct airs_walk w;
-	uint32_t c, a, e = 0, seq_same = 1, m_strided = 1;
-	uint64_t mbase, mstep;
-	uint8_t *h_draws = NULL, *h_seq = NULL, *scr, *h_seq0 = NULL;
-	uint64_t *h_ids = NULL;
-
-	if (!model_needed(P) || !P->uncompressed_fallback_enabled || b->dst_capacity < raw || raw > 0xFFFFFFu ||
-	    (P->primary_preprocessing != CMP_PREPROCESS_NONE && P->primary_preprocessing != CMP_PREPROCESS_DIFF))
-		return WALK_NO;
-	if ((b->flags & CMP_GPU_AUTO_RICE) && P->primary_encoder_type == CMP_ENCODER_GOLOMB_ZERO)
-		return WALK_NO;
-	for (c = 0; c < num_ctx; c++) {
-		const uint32_t sq = ctx[c].sequence_number;
-
-		if (!same_params(&ctx[c].params, P))
-			return WALK_NO;
-		if (sq != 0u && sq <= P->secondary_iterations && ctx[c].model_size != 2u * n)
-			return WALK_NO; /* the reference returns SRC_SIZE_MISMATCH for that frame */
-		if (sq != ctx[0].sequence_number)
-			seq_same = 0;
-	}
-	memset(&w, 0, sizeof(w));
-	w.src = b->src;
-	w.src_stride = b->src_stride;
-	w.sample_bytes = bytes;
-	w.is_unsigned = b->type == CMP_GPU_U16;
-	w.n = n;
-	w.num_ctx = num_ctx;
-	w.fpc = fpc;
-	w.dst = b->dst;
-	w.dst_stride = b->dst_stride;
-	w.cap = raw; /* the first attempt's capacity (cmp.c:358-366) */
-	w.pre_p = P->primary_preprocessing;
-	w.enc_p = P->primary_encoder_type;
-	w.g_p = P->primary_encoder_param;
-	w.outl_p = P->primary_encoder_outlier;
-	w.enc_s = P->secondary_encoder_type;
-	w.g_s = P->secondary_encoder_param;
-	w.outl_s = P->secondary_encoder_outlier;
-	w.model_rate = P->model_rate;
-	w.iters = P->secondary_iterations;
-	w.checksum_enabled = P->checksum_enabled ? 1u : 0u;
-	w.status = b->sizes;
-	w.seq0 = ctx[0].sequence_number;
-	w.fb = 1;
-	w.raw_size = raw;
-	mbase = (uint64_t)(uintptr_t)ctx[0].work_buf;
-	mstep = num_ctx > 1 ? (uint64_t)(uintptr_t)ctx[1].work_buf - mbase : 0;
-	for (c = 0; c < num_ctx && m_strided; c++)
-		m_strided = (uint64_t)(uintptr_t)ctx[c].work_buf == mbase + c * mstep;
-	if (!m_strided)
-		for (c = 0; c < num_ctx; c++)
-			if ((uintptr_t)ctx[c].work_buf & 15u)
-				return WALK_NO;
-	w.model = (void *)(uintptr_t)mbase;
-	w.model_stride = m_strided ? mstep : 0;
-	/* scratch: draws [tb], final sequence numbers [num_ctx], first sequence numbers [num_ctx] */
-	scr = airs_dev_scratch(dev, SLOT_FL, tb + 2u * (size_t)num_ctx + 16u);
-	if (!scr)
-		return ERRV(GENERIC);
-	w.draws = scr;
-	w.seq_out = scr + tb;
-	{
-		struct airs_walk chk = w;
-
-		if (!m_strided)
-			chk.model = NULL, chk.model_stride = 0;
-		if (!airs_dev_walk_supported(&chk))
-			return WALK_NO;
-	}
+	const size_t tb = ((size_t)num_ctx * fpc + 15u) & ~(size_t)15u;
 	/* page-locked host scratch: draws [tb], final sequence numbers [num_ctx]
 	 * (one read-back of the device scratch's first tb + num_ctx bytes), then
 	 * the identifiers [total] at the next 8-byte boundary */
-	{
-		const size_t ioff = (tb + num_ctx + 7u) & ~(size_t)7u;
-		uint8_t *hp = airs_dev_host_scratch(dev, ioff + (size_t)total * 8u);
+	const size_t ioff = (tb + num_ctx + 7u) & ~(size_t)7u;
+	struct walk_prep pr;
+	struct airs_walk *w = &pr.w;
+	uint32_t c, a, e, total, *d_ck;
+	uint8_t *scr, *h_draws, *h_seq;
+	uint64_t *h_ids, *d_ids;
 
-		if (!hp)
-			return ERRV(GENERIC);
-		h_draws = hp;
-		h_seq = hp + tb;
-		h_ids = (uint64_t *)(void *)(hp + ioff);
-	}
-	if (!m_strided) {
-		uint64_t *hp = malloc((size_t)num_ctx * 8u), *d_ptr = airs_dev_scratch(dev, SLOT_AUX, (size_t)num_ctx * 8u);
-
-		if (!hp || !d_ptr)
-			e = ERRV(GENERIC);
-		for (c = 0; c < num_ctx && !is_err(e); c++)
-			hp[c] = (uint64_t)(uintptr_t)ctx[c].work_buf;
-		if (!is_err(e))
-			e = airs_dev_h2d(dev, d_ptr, hp, (size_t)num_ctx * 8u);
-		if (!is_err(e))
-			e = airs_dev_sync(dev);
-		free(hp);
-		w.model_ptrs = d_ptr;
-	}
-	if (!seq_same && !is_err(e)) {
-		uint8_t *d_seq = scr + tb + num_ctx;
-
-		h_seq0 = malloc(num_ctx);
-		if (!h_seq0) {
-			e = ERRV(GENERIC);
-			goto out;
-		}
-		for (c = 0; c < num_ctx; c++)
-			h_seq0[c] = ctx[c].sequence_number;
-		e = airs_dev_h2d(dev, d_seq, h_seq0, num_ctx);
-		if (!is_err(e))
-			e = airs_dev_sync(dev);
-		w.seq0s = d_seq;
-	}
-	if (!is_err(e) && P->checksum_enabled) {
-		uint32_t *d_ck = airs_dev_scratch(dev, SLOT_CK, (size_t)total * 4u);
-
-		e = d_ck ? airs_dev_checksum(dev, b->src, b->src_stride, bytes, n, total, NULL, d_ck) : ERRV(GENERIC);
-		w.checksums = d_ck;
+	if (walk_prepare(ctx, num_ctx, fpc, b, 1, &pr))
+		return WALK_NO;
+	total = pr.total;
+	w->cap = pr.raw; /* the first attempt's capacity (cmp.c:358-366) */
+	w->fb = 1;
+	w->raw_size = pr.raw;
+	/* scratch: draws [tb], final sequence numbers [num_ctx], first sequence
+	 * numbers [num_ctx]; requested before the device is asked, which wants
+	 * to see draws and seq_out */
+	scr = airs_dev_scratch(dev, SLOT_FL, tb + 2u * (size_t)num_ctx + 16u);
+	if (!scr)
+		return ERRV(GENERIC);
+	w->draws = scr;
+	w->seq_out = scr + tb;
+	if (!walk_supported(&pr))
+		return WALK_NO;
+	h_draws = airs_dev_host_scratch(dev, ioff + (size_t)total * 8u);
+	if (!h_draws)
+		return ERRV(GENERIC);
+	h_seq = h_draws + tb;
+	h_ids = (uint64_t *)(void *)(h_draws + ioff);
+	e = walk_upload(dev, &pr, ctx, &ctx[0].sequence_number, sizeof(*ctx), scr + tb + num_ctx, NULL);
+	if (!is_err(e) && w->checksum_enabled) {
+		e = batch_checksums(dev, b, total, &d_ck);
+		w->checksums = d_ck;
 	}
 	if (!is_err(e))
-		e = airs_dev_walk(dev, &w);
+		e = airs_dev_walk(dev, w);
 	/* the one read-back: identifier draws and the final sequence numbers
 	 * (adjacent in the device scratch, one copy into page-locked memory) */
 	if (!is_err(e))
-		e = airs_dev_d2h(dev, h_draws, w.draws, tb + num_ctx);
+		e = airs_dev_d2h(dev, h_draws, w->draws, tb + num_ctx);
 	if (!is_err(e))
 		e = airs_dev_sync(dev);
 	if (is_err(e))
-		goto out;
+		return e;
 	/* the identifiers first; the contexts advance only once the headers are
 	 * patched (a failed upload or patch leaves them as they were) */
-	for (c = 0; c < num_ctx; c++) {
-		uint64_t id = ctx[c].identifier;
-
-		for (a = 0; a < fpc; a++) {
-			const uint32_t f = c * fpc + a;
-
-			for (uint32_t k = 0; k < h_draws[f]; k++)
-				id = next_identifier();
-			ids[f] = id;
-		}
-	}
-	{
-		/* upload from page-locked memory and patch, both asynchronous
-		 * (cmp_gpu_synchronize waits; the next call rewrites the host
-		 * scratch only after its own read-back, which follows them) */
-		uint64_t *d_ids = airs_dev_scratch(dev, SLOT_IDS, (size_t)total * 8u);
-
-		memcpy(h_ids, ids, (size_t)total * 8u);
-		if (!d_ids || is_err(airs_dev_h2d(dev, d_ids, h_ids, (size_t)total * 8u)))
-			e = ERRV(GENERIC);
-		else
-			e = airs_dev_patch_ids(dev, b->dst, b->dst_stride, total, 0, 1, d_ids, b->sizes);
-	}
+	draw_identifiers(ctx, num_ctx, fpc, h_draws, ids, NULL);
+	/* upload from page-locked memory and patch, both asynchronous
+	 * (cmp_gpu_synchronize waits; the next call rewrites the host scratch
+	 * only after its own read-back, which follows them) */
+	d_ids = airs_dev_scratch(dev, SLOT_IDS, (size_t)total * 8u);
+	memcpy(h_ids, ids, (size_t)total * 8u);
+	if (!d_ids || is_err(airs_dev_h2d(dev, d_ids, h_ids, (size_t)total * 8u)))
+		return ERRV(GENERIC);
+	e = airs_dev_patch_ids(dev, b->dst, b->dst_stride, total, 0, 1, d_ids, b->sizes);
 	if (is_err(e))
-		goto out;
+		return e;
 	for (c = 0; c < num_ctx; c++) {
 		for (a = 0; a < fpc; a++)
 			if (REPORT_DRAWS(b))
 				b->draws[c * fpc + a] = h_draws[c * fpc + a];
 		ctx[c].identifier = ids[c * fpc + fpc - 1u];
 		ctx[c].sequence_number = h_seq[c];
-		ctx[c].model_size = 2u * n; /* every context's model holds a frame of this size */
+		ctx[c].model_size = 2u * pr.n; /* every context's model holds a frame of this size */
 	}
-out:
-	free(h_seq0);
 	return e;
 }
 
@@ -1689,141 +1679,58 @@ static uint32_t batch_walk_spec(struct cmp_gpu_engine *eng, struct cmp_context *
 				const struct cmp_gpu_batch *b, const struct pass *pp, const struct pass *ps, uint64_t *ids)
 {
 	struct airs_dev_engine *dev = eng->dev;
-	const struct cmp_params *P = &ctx[0].params;
-	const uint32_t bytes = b->type == CMP_GPU_I16_IN_I32 ? 4u : 2u;
-	const uint32_t n = b->src_size / bytes, total = num_ctx * fpc;
-	const uint32_t raw = raw_frame_size(&ctx[0], n);
-	const size_t mb = 2u * (size_t)n; /* model bytes of a context */
-	struct airs_walk w;
-	uint32_t c, a, e = 0, seq_same = 1, m_strided = 1, msec = 0, cseq = 0, any_redo = 0;
-	uint64_t mbase, mstep;
-	uint8_t *msave, *redo = NULL, *hp;
-	uint32_t *new_seq = NULL;
-	uint64_t *new_id = NULL, *h_ids = NULL;
+	struct walk_prep pr;
+	struct airs_walk *w = &pr.w;
+	uint32_t c, a, e, total, msec = 0, cseq = 0, any_redo = 0, *d_ck;
+	size_t mb; /* model bytes of a context */
+	uint8_t *msave, *redo, *d_seq = NULL;
+	uint32_t *new_seq;
+	uint64_t *new_id, *h_ids;
 
-	if (!model_needed(P) || !P->uncompressed_fallback_enabled || b->dst_capacity < raw || raw > 0xFFFFFFu ||
-	    (P->primary_preprocessing != CMP_PREPROCESS_NONE && P->primary_preprocessing != CMP_PREPROCESS_DIFF))
+	if (num_ctx > AIRS_COMMIT_MAX_CTX || walk_prepare(ctx, num_ctx, fpc, b, 1, &pr))
 		return WALK_NO;
-	if ((b->flags & CMP_GPU_AUTO_RICE) && P->primary_encoder_type == CMP_ENCODER_GOLOMB_ZERO)
+	total = pr.total;
+	mb = 2u * (size_t)pr.n;
+	w->cap = pr.raw; /* the first attempt's capacity; identifiers 0: patched once they are drawn */
+	if (!walk_supported(&pr))
 		return WALK_NO;
-	if (num_ctx > AIRS_COMMIT_MAX_CTX)
-		return WALK_NO;
-	for (c = 0; c < num_ctx; c++) {
-		const uint32_t sq = ctx[c].sequence_number;
-
-		if (!same_params(&ctx[c].params, P))
-			return WALK_NO;
-		if (sq != 0u && sq <= P->secondary_iterations && ctx[c].model_size != 2u * n)
-			return WALK_NO; /* the reference returns SRC_SIZE_MISMATCH for that frame */
-		if (sq != ctx[0].sequence_number)
-			seq_same = 0;
-	}
-	memset(&w, 0, sizeof(w));
-	w.src = b->src;
-	w.src_stride = b->src_stride;
-	w.sample_bytes = bytes;
-	w.is_unsigned = b->type == CMP_GPU_U16;
-	w.n = n;
-	w.num_ctx = num_ctx;
-	w.fpc = fpc;
-	w.dst = b->dst;
-	w.dst_stride = b->dst_stride;
-	w.cap = raw; /* the first attempt's capacity */
-	w.pre_p = P->primary_preprocessing;
-	w.enc_p = P->primary_encoder_type;
-	w.g_p = P->primary_encoder_param;
-	w.outl_p = P->primary_encoder_outlier;
-	w.enc_s = P->secondary_encoder_type;
-	w.g_s = P->secondary_encoder_param;
-	w.outl_s = P->secondary_encoder_outlier;
-	w.model_rate = P->model_rate;
-	w.iters = P->secondary_iterations;
-	w.checksum_enabled = P->checksum_enabled ? 1u : 0u;
-	w.status = b->sizes;
-	w.seq0 = ctx[0].sequence_number;
-	mbase = (uint64_t)(uintptr_t)ctx[0].work_buf;
-	mstep = num_ctx > 1 ? (uint64_t)(uintptr_t)ctx[1].work_buf - mbase : 0;
-	for (c = 0; c < num_ctx && m_strided; c++)
-		m_strided = (uint64_t)(uintptr_t)ctx[c].work_buf == mbase + c * mstep;
-	if (!m_strided)
-		for (c = 0; c < num_ctx; c++)
-			if ((uintptr_t)ctx[c].work_buf & 15u)
-				return WALK_NO;
-	w.model = (void *)(uintptr_t)mbase;
-	w.model_stride = m_strided ? mstep : 0;
-	/* identifiers 0: patched once they are drawn */
-	{
-		struct airs_walk chk = w;
-
-		if (!m_strided)
-			chk.model = NULL, chk.model_stride = 0;
-		if (!airs_dev_walk_supported(&chk))
-			return WALK_NO;
-	}
 	/* page-locked host scratch: the identifiers for patch_ids_kernel (when
 	 * the commit kernel does not take them) */
 	msave = airs_dev_scratch(dev, SLOT_MSAVE, mb * num_ctx);
-	hp = airs_dev_host_scratch(dev, (size_t)total * 8u);
+	h_ids = airs_dev_host_scratch(dev, (size_t)total * 8u);
 	new_seq = calloc(num_ctx, sizeof(*new_seq));
 	new_id = calloc(num_ctx, sizeof(*new_id));
 	redo = calloc(num_ctx, 1);
-	if (!msave || !hp || !new_seq || !new_id || !redo) {
+	if (!msave || !h_ids || !new_seq || !new_id || !redo) {
 		e = ERRV(GENERIC);
 		goto out;
 	}
-	if (!m_strided) {
-		uint64_t *hp = malloc((size_t)num_ctx * 8u), *d_ptr = airs_dev_scratch(dev, SLOT_AUX, (size_t)num_ctx * 8u);
-
-		if (!hp || !d_ptr)
-			e = ERRV(GENERIC);
-		for (c = 0; c < num_ctx && !is_err(e); c++)
-			hp[c] = (uint64_t)(uintptr_t)ctx[c].work_buf;
-		if (!is_err(e))
-			e = airs_dev_h2d(dev, d_ptr, hp, (size_t)num_ctx * 8u);
-		if (!is_err(e))
-			e = airs_dev_sync(dev);
-		free(hp);
-		w.model_ptrs = d_ptr;
-	}
-	if (!seq_same && !is_err(e)) {
-		uint8_t *hs = malloc(num_ctx), *d_seq = airs_dev_scratch(dev, SLOT_FL, num_ctx);
-
-		if (!hs || !d_seq)
-			e = ERRV(GENERIC);
-		for (c = 0; c < num_ctx && !is_err(e); c++)
-			hs[c] = ctx[c].sequence_number;
-		if (!is_err(e))
-			e = airs_dev_h2d(dev, d_seq, hs, num_ctx);
-		if (!is_err(e))
-			e = airs_dev_sync(dev);
-		free(hs);
-		w.seq0s = d_seq;
-	}
+	if (!pr.seq_same)
+		d_seq = airs_dev_scratch(dev, SLOT_FL, num_ctx);
+	e = walk_upload(dev, &pr, ctx, &ctx[0].sequence_number, sizeof(*ctx), d_seq, NULL);
 	/* the models as they are before the launch, for contexts run again whose
 	 * first frame reads its model (a secondary pass; a primary pass stores
 	 * the model without reading it) */
 	for (c = 0; c < num_ctx; c++)
-		if (ctx[c].sequence_number != 0u && ctx[c].sequence_number <= w.iters)
+		if (ctx[c].sequence_number != 0u && ctx[c].sequence_number <= w->iters)
 			msec = 1;
 	if (!is_err(e) && msec) {
-		if (m_strided)
-			e = airs_dev_d2d_rows(dev, msave, mb, ctx[0].work_buf, num_ctx > 1 ? mstep : mb, mb, num_ctx);
+		if (pr.m_strided)
+			e = airs_dev_d2d_rows(dev, msave, mb, ctx[0].work_buf, num_ctx > 1 ? w->model_stride : mb, mb,
+					      num_ctx);
 		else
 			for (c = 0; c < num_ctx && !is_err(e); c++)
 				e = airs_dev_d2d_rows(dev, msave + c * mb, mb, ctx[c].work_buf, mb, mb, 1);
 	}
-	if (!is_err(e) && P->checksum_enabled) {
-		uint32_t *d_ck = airs_dev_scratch(dev, SLOT_CK, (size_t)total * 4u);
-
-		e = d_ck ? airs_dev_checksum(dev, b->src, b->src_stride, bytes, n, total, NULL, d_ck) : ERRV(GENERIC);
-		w.checksums = d_ck;
+	if (!is_err(e) && w->checksum_enabled) {
+		e = batch_checksums(dev, b, total, &d_ck);
+		w->checksums = d_ck;
 	}
 	/* the one round trip: which contexts have a frame that did not fit.  The
 	 * commit kernel signals them, then waits on the stream for the release
 	 * below (it patches the identifiers when no context runs again) */
-	h_ids = (uint64_t *)(void *)hp;
 	if (!is_err(e))
-		e = airs_dev_walk(dev, &w);
+		e = airs_dev_walk(dev, w);
 	if (!is_err(e)) {
 		e = airs_dev_commit_begin(dev, b->sizes, num_ctx, fpc, b->dst, b->dst_stride, &cseq);
 		if (!is_err(e)) {
@@ -1848,7 +1755,7 @@ static uint32_t batch_walk_spec(struct cmp_gpu_engine *eng, struct cmp_context *
 			uint64_t id = ctx[c].identifier;
 
 			for (a = 0; a < fpc; a++) {
-				const int prim = sq == 0u || sq > w.iters;
+				const int prim = sq == 0u || sq > w->iters;
 
 				if (prim)
 					id = next_identifier();
@@ -1889,7 +1796,7 @@ static uint32_t batch_walk_spec(struct cmp_gpu_engine *eng, struct cmp_context *
 			continue; /* committed by batch_device_exact */
 		ctx[c].identifier = new_id[c];
 		ctx[c].sequence_number = (uint8_t)new_seq[c];
-		ctx[c].model_size = 2u * n;
+		ctx[c].model_size = 2u * pr.n;
 	}
 out:
 	free(new_seq);
@@ -1907,7 +1814,6 @@ out:
  * frames' coefficients go to device scratch (at most IWT_SCRATCH_MAX bytes,
  * else WALK_NO: the per-acquisition launches).
  */
-#define IWT_SCRATCH_MAX (1ull << 30)
 static uint32_t batch_iwt(struct cmp_gpu_engine *eng, struct cmp_context *ctx, uint32_t num_ctx, uint32_t fpc,
 			  const struct cmp_gpu_batch *b, const struct frame_plan *plan, uint64_t *ids, uint64_t *ptrs)
 {
@@ -2039,7 +1945,7 @@ uint32_t cmp_gpu_compress(struct cmp_gpu_engine *eng, struct cmp_context *ctx, u
 		 * identifier draws; a frame the host API would reject sends the
 		 * batch to the step-by-step path with the contexts untouched */
 		struct cmp_context *snap = malloc((size_t)num_ctx * sizeof(*snap));
-		uint32_t *draws = calloc(total, sizeof(uint32_t));
+		uint8_t *draws = calloc(total, 1);
 
 		if (!snap || !draws) {
 			free(snap);
@@ -2052,31 +1958,26 @@ uint32_t cmp_gpu_compress(struct cmp_gpu_engine *eng, struct cmp_context *ctx, u
 			for (a = 0; a < fpc; a++) {
 				const uint32_t f = c * fpc + a;
 				void *dst = (uint8_t *)b->dst + (uint64_t)f * b->dst_stride;
+				uint32_t drawn = 0;
 
-				if (is_err(engine_prologue(&ctx[c], dst, b->dst_capacity, n, &plan[f].p, &draws[f]))) {
+				if (is_err(engine_prologue(&ctx[c], dst, b->dst_capacity, n, &plan[f].p, &drawn))) {
 					exact = 1;
 					break;
 				}
+				draws[f] = (uint8_t)drawn;
 				ctx[c].sequence_number++;
 			}
 		}
 		if (exact) {
 			memcpy(ctx, snap, (size_t)num_ctx * sizeof(*snap));
 		} else {
-			/* the identifiers, drawn in call order */
+			/* the identifiers, drawn in call order (the replay's resets
+			 * cleared the contexts': they start from the snapshot's) */
+			draw_identifiers(snap, num_ctx, fpc, draws, ids, REPORT_DRAWS(b) ? b->draws : NULL);
 			for (c = 0; c < num_ctx; c++) {
-				uint64_t id = snap[c].identifier;
-
-				for (a = 0; a < fpc; a++) {
-					const uint32_t f = c * fpc + a;
-
-					for (uint32_t k = 0; k < draws[f]; k++)
-						id = next_identifier();
-					plan[f].id = id;
-					if (REPORT_DRAWS(b))
-						b->draws[f] = (uint8_t)draws[f];
-				}
-				ctx[c].identifier = id;
+				for (a = 0; a < fpc; a++)
+					plan[c * fpc + a].id = ids[c * fpc + a];
+				ctx[c].identifier = ids[c * fpc + fpc - 1u];
 			}
 		}
 		free(snap);
@@ -2122,7 +2023,7 @@ uint32_t cmp_gpu_compress(struct cmp_gpu_engine *eng, struct cmp_context *ctx, u
 			   (e = batch_iwt(eng, ctx, num_ctx, fpc, b, plan, ids, ptrs)) != WALK_NO) {
 			/* IWT contexts: every frame in one launch (or an error) */
 		} else if (any_model && !(b->flags & CMP_GPU_STEPWISE) &&
-			   (e = batch_walk(eng, ctx, num_ctx, fpc, b, plan)) != WALK_NO) {
+			   (e = batch_walk(eng, ctx, num_ctx, fpc, b, plan, ids)) != WALK_NO) {
 			/* every acquisition in one launch (or an error) */
 		} else {
 			e = 0;

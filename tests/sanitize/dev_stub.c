@@ -7,8 +7,12 @@
  * sanitizer row).  It does not encode anything: an "encode" writes a
  * deterministic pseudo-random outcome per frame (a size that fits, or
  * CMP_ERR_DST_TOO_SMALL) plus a header-shaped first 16 bytes, which is
- * enough to drive every branch of the planner.  Device memory is malloc'd
- * host memory, copies are memcpy.  Never linked into the product.
+ * enough to drive every branch of the planner.  The walk (airs_dev_walk)
+ * refuses and fails as the device does where the planner depends on it: the
+ * fallback on the chip only for the context walk's batches, and without it
+ * DST_TOO_SMALL for a frame past the capacity, so all three MODEL batch paths
+ * and the redo of a context run.  Device memory is malloc'd host memory,
+ * copies are memcpy.  Never linked into the product.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -152,6 +156,14 @@ uint32_t airs_dev_encode(struct airs_dev_engine *e, const struct airs_launch *L)
 	return 0;
 }
 
+/* The device resolves the fallback on the chip (w->fb) only in the context
+ * walk: frames of that walk's size and enough contexts to fill the CUs
+ * (ctx_walk_words, encode.hip).  These two stand in for that rule at the
+ * harness's sizes, so that the host's fall-through from batch_walk_fb to
+ * batch_walk_spec is exercised as written. */
+#define STUB_CTX_WALK_SAMPLES 8192u
+#define STUB_CTX_WALK_MIN_CTX 3u
+
 /* the walk needs n % 4096 == 0 and 16-byte aligned inputs; the stub checks
  * the same so that the host's applicability test is exercised as written */
 int airs_dev_walk_supported(const struct airs_walk *w)
@@ -160,7 +172,8 @@ int airs_dev_walk_supported(const struct airs_walk *w)
 		return 0;
 	if (((uintptr_t)w->src & 15u) || (w->src_stride & 15u))
 		return 0;
-	if (w->fb && (!w->draws || !w->seq_out || w->cap != w->raw_size))
+	if (w->fb && (!w->draws || !w->seq_out || w->cap != w->raw_size || w->n != STUB_CTX_WALK_SAMPLES ||
+		      w->num_ctx < STUB_CTX_WALK_MIN_CTX))
 		return 0;
 	return w->model_ptrs || !(((uintptr_t)w->model & 15u) || (w->model_stride & 15u));
 }
@@ -191,8 +204,18 @@ uint32_t airs_dev_walk(struct airs_dev_engine *e, struct airs_walk *w)
 				(void)w->ids[f];
 			if (w->checksum_enabled && w->checksums)
 				(void)w->checksums[f];
-			if (size > w->cap)
+			if (size > w->cap) {
+				/* the segment walk reports a frame that did not fit (the
+				 * host runs its context again); with fb the walk resolves
+				 * the fallback itself and every frame has a size.  In the
+				 * asynchronous mode cap is at least the frame bound,
+				 * 26 + 6n, above the largest size here, 16 + 3n + 7. */
+				if (!w->fb) {
+					w->status[f] = ERRV(30u); /* DST_TOO_SMALL */
+					continue;
+				}
 				size = w->cap;
+			}
 			memset(dst, 0, 16);
 			dst[size - 1u] = 0x5A;
 			w->status[f] = size;

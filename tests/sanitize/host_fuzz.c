@@ -6,6 +6,7 @@
  * dev_stub.c).  Any sanitizer report aborts the run with a non-zero status;
  * tests/test_sanitize_cpu.py runs it.  usage: host_fuzz [iterations] [seed]
  */
+#include <sanitizer/asan_interface.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,6 +15,8 @@
 #include "cmp.h"
 #include "cmp_errors.h"
 #include "cmp_gpu.h"
+#include "cmp_header.h"
+#include "airs_dev.h"
 #include "params_parse.h"
 
 static uint64_t g_rng;
@@ -113,6 +116,46 @@ static void fuzz_host_api(void)
 	free(src);
 }
 
+/* 64-bit FNV-1a over what every batch call of the run returned: two builds
+ * of the library that plan alike print the same digest for the same seed */
+static uint64_t g_digest = 0xCBF29CE484222325ull;
+
+static void fold(const void *data, size_t len)
+{
+	const uint8_t *d = data;
+
+	while (len--)
+		g_digest = (g_digest ^ *d++) * 0x100000001B3ull;
+}
+
+static void fold_u64(uint64_t v)
+{
+	fold(&v, sizeof(v));
+}
+
+/* one cmp_gpu_compress call: its return value, the size and draw count of
+ * every frame, the head of every frame that has a size, the contexts' state */
+static void fold_call(uint32_t r, const struct cmp_gpu_batch *b, const struct cmp_context *ctx, uint32_t nctx,
+		      uint32_t nf)
+{
+	uint32_t i;
+
+	fold_u64(r);
+	if (b) {
+		fold(b->sizes, (size_t)nf * 4u);
+		if (b->draws)
+			fold(b->draws, nf);
+		for (i = 0; i < nf; i++)
+			if (!cmp_is_error(b->sizes[i]))
+				fold((const uint8_t *)b->dst + (uint64_t)i * b->dst_stride, 16);
+	}
+	for (i = 0; ctx && i < nctx; i++) {
+		fold_u64(ctx[i].identifier);
+		fold_u64(ctx[i].sequence_number);
+		fold_u64(ctx[i].model_size);
+	}
+}
+
 /* batch API: the planner, exact (step-by-step) and asynchronous modes */
 static void fuzz_batch(struct cmp_gpu_engine *eng)
 {
@@ -123,8 +166,9 @@ static void fuzz_batch(struct cmp_gpu_engine *eng)
 	 * walk path (airs_dev_walk) becomes applicable */
 	const uint32_t n = pick(4) ? 1u + pick(pick(2) ? 40 : 3000) : 4096u * (1u + pick(2));
 	struct cmp_context *ctx = calloc(nctx, sizeof(*ctx));
-	uint8_t **work = calloc(nctx, sizeof(*work));
-	uint32_t *sizes = calloc(nf, 4u), c, wbs, ok = 1;
+	uint8_t *work[4] = { NULL, NULL, NULL, NULL }, *slab = NULL;
+	size_t slab_size = 0;
+	uint32_t *sizes = calloc(nf, 4u), c, wbs, r, ok = 1;
 	const uint64_t stride = ((uint64_t)n * sb + 15u) & ~15ull;
 	uint8_t *src = malloc(stride * nf);
 	uint32_t bound, cap;
@@ -141,12 +185,37 @@ static void fuzz_batch(struct cmp_gpu_engine *eng)
 	if (pick(2))
 		cap = 16u + pick(cap);
 	dstride = ((uint64_t)(cmp_is_error(bound) ? cap : bound) + 64u + 7u) & ~7ull;
-	dst = malloc(dstride * nf);
+	dst = calloc(dstride, nf); /* zeroed: the digest reads the head of every frame */
 	wbs = cmp_cal_work_buf_size(&p, 2u * n);
+	if (!cmp_is_error(wbs) && wbs) {
+		/* The work buffers lie in one slab at offsets drawn here, so the
+		 * planner's model addressing does not depend on the heap: equal
+		 * 16-aligned spacing (the strided form), unequal spacing (from three
+		 * contexts on: the pointer list), or unequal with one buffer 2 bytes
+		 * off (refused: the walk wants 16-byte aligned models).  The gaps
+		 * between the buffers are poisoned. */
+		const uint32_t layout = pick(8), odd = pick(nctx);
+		const size_t wstep = (((size_t)wbs + 15u) & ~(size_t)15u) + 16u * (1u + pick(3));
+		size_t off = 0;
+
+		slab_size = (size_t)nctx * (wstep + 16u);
+		if (posix_memalign((void **)&slab, 16, slab_size))
+			abort();
+		memset(slab, 0, slab_size);
+		ASAN_POISON_MEMORY_REGION(slab, slab_size);
+		for (c = 0; c < nctx; c++) {
+			work[c] = slab + off + (layout == 0 && c == odd ? 2u : 0u);
+			ASAN_UNPOISON_MEMORY_REGION(work[c], wbs);
+			off += wstep + (layout < 4 ? 16u * (c & 1u) : 0u);
+		}
+	}
 	for (c = 0; c < nctx; c++) {
-		if (!cmp_is_error(wbs) && wbs)
-			work[c] = calloc(wbs + 16u, 1);
-		if (cmp_is_error(cmp_initialise(&ctx[c], &p, work[c], cmp_is_error(wbs) ? 0 : wbs)))
+		struct cmp_params q = p;
+
+		/* now and then the last context has parameters of its own */
+		if (c && c + 1u == nctx && !pick(16))
+			q.model_rate = p.model_rate ? p.model_rate - 1u : 1u;
+		if (cmp_is_error(cmp_initialise(&ctx[c], &q, work[c], cmp_is_error(wbs) ? 0 : wbs)))
 			ok = 0;
 	}
 	memset(&b, 0, sizeof(b));
@@ -165,15 +234,29 @@ static void fuzz_batch(struct cmp_gpu_engine *eng)
 	if (draws)
 		b.flags |= CMP_GPU_REPORT_DRAWS;
 	if (ok) {
-		if (!cmp_is_error(cmp_gpu_compress(eng, ctx, nctx, fpc, &b))) {
+		/* now and then context 0 is one frame ahead of the others, at
+		 * times a frame of half the size (its model then has another size
+		 * than the batch's frames) */
+		if (!pick(4)) {
+			if (n % 2u == 0 && !pick(3))
+				b.src_size = n / 2u * sb;
+			r = cmp_gpu_compress(eng, ctx, 1, 1, &b);
+			fold_call(r, &b, ctx, nctx, nf);
+			b.src_size = n * sb;
+		}
+		r = cmp_gpu_compress(eng, ctx, nctx, fpc, &b);
+		fold_call(r, &b, ctx, nctx, nf);
+		if (!cmp_is_error(r)) {
 			n_batch_ok++;
 			for (c = 0; c < nf; c++)
 				n_batch_frames_ok += !cmp_is_error(sizes[c]);
 			n_batch_fallback_cap += p.uncompressed_fallback_enabled;
 		}
 		/* a second call continues the contexts' pass sequence */
-		if (pick(2))
-			(void)cmp_gpu_compress(eng, ctx, nctx, fpc, &b);
+		if (pick(2)) {
+			r = cmp_gpu_compress(eng, ctx, nctx, fpc, &b);
+			fold_call(r, &b, ctx, nctx, nf);
+		}
 		(void)cmp_gpu_synchronize(eng);
 	}
 	/* payload-only stream over the batch's samples */
@@ -182,27 +265,73 @@ static void fuzz_batch(struct cmp_gpu_engine *eng)
 		const uint32_t st = pick(5) ? type : pick(9), ssb = st == 2 ? 4u : 2u;
 		/* at most the samples the batch buffer holds */
 		const uint32_t sn = (uint32_t)(stride * nf / ssb);
-		const uint32_t r = cmp_gpu_encode_stream(eng, (enum cmp_gpu_sample_type)st,
-							 pick(20) ? src : NULL, pick(20) ? 1u + pick(sn) : 0,
-							 (enum cmp_preprocessing)pick(5), (enum cmp_encoder_type)pick(4),
-							 pick(8) ? 1u + pick(70) : pick(70000), pick(300), pick(20) ? dst : NULL,
-							 pick(2) ? cap : (uint32_t)(dstride * nf), &ssz);
+		r = cmp_gpu_encode_stream(eng, (enum cmp_gpu_sample_type)st, pick(20) ? src : NULL,
+					  pick(20) ? 1u + pick(sn) : 0, (enum cmp_preprocessing)pick(5),
+					  (enum cmp_encoder_type)pick(4), pick(8) ? 1u + pick(70) : pick(70000), pick(300),
+					  pick(20) ? dst : NULL, pick(2) ? cap : (uint32_t)(dstride * nf), &ssz);
 		n_stream_ok += !cmp_is_error(r) && !cmp_is_error(ssz);
 	}
 	/* argument errors */
 	b.dst_stride = pick(2) ? 1 : dstride;
 	b.src_size = pick(2) ? 3 : n * sb;
-	(void)cmp_gpu_compress(eng, ctx, nctx, fpc, &b);
-	(void)cmp_gpu_compress(eng, NULL, nctx, fpc, &b);
-	(void)cmp_gpu_compress(eng, ctx, nctx, fpc, NULL);
-	for (c = 0; c < nctx; c++)
-		free(work[c]);
-	free(work);
+	r = cmp_gpu_compress(eng, ctx, nctx, fpc, &b);
+	fold_call(r, &b, ctx, nctx, nf);
+	r = cmp_gpu_compress(eng, NULL, nctx, fpc, &b);
+	fold_call(r, &b, NULL, 0, nf);
+	r = cmp_gpu_compress(eng, ctx, nctx, fpc, NULL);
+	fold_call(r, NULL, ctx, nctx, nf);
+	if (slab)
+		ASAN_UNPOISON_MEMORY_REGION(slab, slab_size);
+	free(slab);
 	free(ctx);
 	free(sizes);
 	free(src);
 	free(dst);
 	free(draws);
+}
+
+/* once per run: one context more than a commit kernel flags
+ * (AIRS_COMMIT_MAX_CTX), so the batch leaves the segment walk's fallback path
+ * for the per-acquisition device state machine */
+static void fuzz_many_contexts(struct cmp_gpu_engine *eng)
+{
+	const uint32_t nctx = AIRS_COMMIT_MAX_CTX + 1u, n = 4096u;
+	struct cmp_context *ctx = calloc(nctx, sizeof(*ctx));
+	uint8_t *work = calloc(nctx, 2u * n), *src = calloc(nctx, 2u * n);
+	struct cmp_params p;
+	struct cmp_gpu_batch b;
+	uint32_t c, r;
+
+	memset(&p, 0, sizeof(p));
+	p.primary_preprocessing = CMP_PREPROCESS_DIFF;
+	p.primary_encoder_type = CMP_ENCODER_GOLOMB_ZERO;
+	p.primary_encoder_param = 32;
+	p.secondary_iterations = 2;
+	p.secondary_preprocessing = CMP_PREPROCESS_MODEL;
+	p.secondary_encoder_type = CMP_ENCODER_GOLOMB_ZERO;
+	p.secondary_encoder_param = 8;
+	p.model_rate = 11;
+	p.uncompressed_fallback_enabled = 1;
+	for (c = 0; c < nctx; c++)
+		if (cmp_is_error(cmp_initialise(&ctx[c], &p, work + (size_t)c * 2u * n, 2u * n)))
+			abort();
+	memset(&b, 0, sizeof(b));
+	b.type = CMP_GPU_U16;
+	b.src = src;
+	b.src_stride = 2u * n;
+	b.src_size = 2u * n;
+	b.dst_capacity = CMP_HDR_SIZE + 2u * n; /* the raw frame: the first attempt's capacity */
+	b.dst_stride = b.dst_capacity;
+	b.dst = calloc(nctx, b.dst_stride);
+	b.sizes = calloc(nctx, 4u);
+	r = cmp_gpu_compress(eng, ctx, nctx, 1, &b);
+	fold_call(r, &b, ctx, nctx, nctx);
+	(void)cmp_gpu_synchronize(eng);
+	free(ctx);
+	free(work);
+	free(src);
+	free(b.dst);
+	free(b.sizes);
 }
 
 /* CLI --params grammar: valid strings, mutated and truncated */
@@ -280,6 +409,7 @@ int main(int argc, char **argv)
 		fprintf(stderr, "engine create failed\n");
 		return 2;
 	}
+	fuzz_many_contexts(eng);
 	for (i = 0; i < iters; i++) {
 		fuzz_host_api();
 		fuzz_batch(eng);
@@ -289,8 +419,8 @@ int main(int argc, char **argv)
 	cmp_gpu_engine_destroy(eng);
 	printf("gather plans: %u ok, %u refused\n", n_plan_ok, n_plan_refused);
 	printf("host_fuzz: %u iterations clean: %u contexts initialised, host frames %u ok / %u errors, "
-	       "%u batches (%u frames ok, %u with fallback enabled), %u streams, %lu walks\n",
+	       "%u batches (%u frames ok, %u with fallback enabled), %u streams, %lu walks, digest %016llx\n",
 	       iters, n_init_ok, n_frames_ok, n_frames_err, n_batch_ok, n_batch_frames_ok, n_batch_fallback_cap,
-	       n_stream_ok, stub_walk_calls);
+	       n_stream_ok, stub_walk_calls, (unsigned long long)g_digest);
 	return 0;
 }
