@@ -461,22 +461,173 @@ __device__ __forceinline__ uint2 rice_table_entry(uint32_t q, uint32_t k)
 	return make_uint2(t, k + 1u + q);
 }
 
-// First look-back round's granule loads (wave 0, not the frame's first
-// segment): LB_WIN windows of 64 aggregates, newest first, and the
-// predecessor's tail.  Addresses are clamped into the frame instead of
-// predicated, so the loads need no exec-mask branch (a predicated load made
-// the compiler wait for it right away); the evaluation ignores the clamped
-// lanes.
-template <int LB_WIN>
-__device__ __forceinline__ void lb_prefetch(const KArgs &a, uint64_t (&gv)[LB_WIN], uint64_t &tv0, uint32_t gseg,
-					    uint32_t first_seg, uint32_t lane)
+// ---------------------------------------------------------------------
+// The decoupled look-back (wave 0 of a segment that is not its frame's
+// first): the segment's frame bit offset (header bits
+// included) from its predecessors' `agg` granules, and the predecessor's
+// last 32 bits from its `tail` granule.  A window is 64 granules, lane l
+// holding granule gseg - 1 - l (newest first).  A kernel chooses when its
+// first window is read (lb_prefetch: vector loads, issued early; lb_scalar:
+// scalar loads, read on the spot) and publishes its own granules; the rest
+// is lb_resolve.  Every wait is bounded (AIRS_SPIN_LIMIT, the fault word).
+// ---------------------------------------------------------------------
+struct LbWin {
+	uint64_t gv; // this lane's granule of the window
+	uint64_t tv; // the predecessor's tail granule
+};
+#ifndef AIRS_LB_SCALAR_N // granules of the scalar first look-back round (16 or 32)
+#define AIRS_LB_SCALAR_N 16
+#endif
+
+// First window by vector loads, and the predecessor's tail.  Addresses are
+// clamped into the frame instead of predicated, so the loads need no
+// exec-mask branch (a predicated load made the compiler wait for it right
+// away); the evaluation ignores the clamped lanes.
+__device__ __forceinline__ LbWin lb_prefetch(const KArgs &a, uint32_t gseg, uint32_t first_seg, uint32_t lane)
 {
+	LbWin w;
+	const int64_t idx = (int64_t)gseg - 1 - (int64_t)lane;
+	w.gv = gran_load(&a.agg[idx >= (int64_t)first_seg ? idx : (int64_t)first_seg]);
+	w.tv = gran_load(&a.tail[gseg - 1u]);
+	return w;
+}
+
+// a granule address in SGPRs (uniform, but not known to the compiler to be)
+__device__ __forceinline__ const uint64_t *lb_sptr(const uint64_t *p)
+{
+	const uint64_t v = (uint64_t)(uintptr_t)p;
+	const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)v);
+	const uint32_t h = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+	return (const uint64_t *)(uintptr_t)(((uint64_t)h << 32) | l);
+}
+
+// First window by scalar loads (sif >= AIRS_LB_SCALAR_N): the newest
+// AIRS_LB_SCALAR_N granules and the tail through the scalar cache path (glc:
+// no scalar-cache hit), which does not queue behind the CU's sample loads.
+// One asm statement with its wait: no register of an outstanding load is
+// visible to the compiler (lgkmcnt also counts LDS
+// operations).  Lanes >= AIRS_LB_SCALAR_N take gearly, a window read earlier
+// (any published granule stays true), or 0: they read as unpublished and send
+// the round to the vector loads unless an inclusive granule comes first.
+__device__ __forceinline__ LbWin lb_scalar(const KArgs &a, uint32_t gseg, uint32_t lane, uint64_t gearly)
+{
+	constexpr uint32_t SLB_N = AIRS_LB_SCALAR_N;
+	static_assert(SLB_N == 16u || SLB_N == 32u, "two or four s_load_dwordx16");
+	typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+	const uint64_t *gp = lb_sptr(&a.agg[gseg - SLB_N]);
+	const uint64_t *tp = lb_sptr(&a.tail[gseg - 1u]);
+	// q[b]: granules gseg - SLB_N + 8 b .. + 7 -> lanes SLB_N - 1 - (8 b + i)
+	u32x16 q[SLB_N / 8u];
+	uint64_t tq;
+	if constexpr (SLB_N == 32u)
+		asm volatile("s_load_dwordx16 %0, %5, 0x0 glc\n\t"
+			     "s_load_dwordx16 %1, %5, 0x40 glc\n\t"
+			     "s_load_dwordx16 %2, %5, 0x80 glc\n\t"
+			     "s_load_dwordx16 %3, %5, 0xc0 glc\n\t"
+			     "s_load_dwordx2 %4, %6, 0x0 glc\n\t"
+			     "s_waitcnt lgkmcnt(0)"
+			     : "=&s"(q[0]), "=&s"(q[1]), "=&s"(q[2]), "=&s"(q[3]), "=&s"(tq)
+			     : "s"(gp), "s"(tp)
+			     : "memory");
+	else
+		asm volatile("s_load_dwordx16 %0, %3, 0x0 glc\n\t"
+			     "s_load_dwordx16 %1, %3, 0x40 glc\n\t"
+			     "s_load_dwordx2 %2, %4, 0x0 glc\n\t"
+			     "s_waitcnt lgkmcnt(0)"
+			     : "=&s"(q[0]), "=&s"(q[1]), "=&s"(tq)
+			     : "s"(gp), "s"(tp)
+			     : "memory");
+	uint32_t vl = (uint32_t)gearly, vh = (uint32_t)(gearly >> 32);
 #pragma unroll
-	for (int w = 0; w < LB_WIN; w++) {
-		const int64_t idx = (int64_t)gseg - 1 - 64 * w - (int64_t)lane;
-		gv[w] = gran_load(&a.agg[idx >= (int64_t)first_seg ? idx : (int64_t)first_seg]);
+	for (uint32_t i = 0; i < SLB_N; i++) {
+		vl = lane == SLB_N - 1u - i ? q[i >> 3][2u * (i & 7u)] : vl;
+		vh = lane == SLB_N - 1u - i ? q[i >> 3][2u * (i & 7u) + 1u] : vh;
 	}
-	tv0 = gran_load(&a.tail[gseg - 1u]);
+	LbWin w;
+	w.gv = ((uint64_t)vh << 32) | vl;
+	w.tv = tq;
+	return w;
+}
+
+// Wait for the predecessor's tail granule, from a first read tv of it: (its
+// last 32 bits, the re-reads it took).  Lane 0's copy is the one used.
+__device__ __forceinline__ uint2 lb_tail_wait(const KArgs &a, uint32_t gseg, uint32_t lane, uint64_t tv)
+{
+	uint32_t polls = 0;
+	for (; (uint32_t)(tv >> 32) != a.epoch; polls++) {
+		if (polls > AIRS_SPIN_LIMIT) {
+			if (lane == 0)
+				atomicAdd(a.ticket + AIRS_FAULT_WORD, 1u); // never expected (the host reports it)
+			break;
+		}
+		__builtin_amdgcn_s_sleep(1);
+		tv = gran_load(&a.tail[gseg - 1u]);
+	}
+	return make_uint2((uint32_t)tv, polls);
+}
+
+// Evaluate a look-back from a first window (gv: granule gseg - 1 - lane,
+// newest first; tv: the predecessor's tail granule), reloading with vector
+// loads until the segment's frame bit offset is known: (offset, the
+// predecessor's last 32 bits).  Every published granule stays true, so the
+// first window may be of any age.
+__device__ __forceinline__ uint2 lb_resolve(const KArgs &a, uint32_t gseg, uint32_t sif, uint32_t lane, uint64_t gv,
+					    uint64_t tv, uint32_t rounds)
+{
+	const uint32_t first_seg = gseg - sif;
+	uint32_t sum = 0u, spins = 0u;
+	int64_t j = (int64_t)gseg - 1;
+	for (;;) {
+		const int64_t idx = j - (int64_t)lane;
+		const bool inr = idx >= (int64_t)first_seg;
+		const uint32_t tag = (uint32_t)(gv >> 32);
+		const bool valid = inr && (tag >> 1) == a.epoch;
+		const bool incl = valid && (tag & 1u);
+		const uint64_t incl_m = __ballot(incl);
+		const uint64_t bad_m = __ballot(inr && !valid);
+		const uint32_t fi = incl_m ? (uint32_t)__ffsll((unsigned long long)incl_m) - 1u : 64u;
+		const uint64_t need = fi >= 63u ? ~0ull : ((2ull << fi) - 1ull);
+		if (!(bad_m & need)) {
+			sum += wave_sum((inr && lane <= fi) ? (uint32_t)gv : 0u);
+			if (incl_m)
+				break;
+			j -= 64; // every granule of this window is an aggregate: the next window
+			rounds++;
+		} else if (++spins > AIRS_SPIN_LIMIT) {
+			if (lane == 0)
+				atomicAdd(a.ticket + AIRS_FAULT_WORD, 1u); // never expected (the host reports it)
+			break;
+		} else {
+			__builtin_amdgcn_s_sleep(1); // a needed predecessor has not published: re-poll
+			rounds++;
+		}
+		const int64_t nidx = j - (int64_t)lane;
+		gv = gran_load(&a.agg[nidx >= (int64_t)first_seg ? nidx : (int64_t)first_seg]);
+	}
+	const uint2 tw = lb_tail_wait(a, gseg, lane, tv);
+	if (DBG(65536u) && !DBG(262144u) && a.dbgts && lane == 0) {
+		a.dbgts[8u * gseg + 5u] = ((uint64_t)spins << 32) | rounds;
+		a.dbgts[8u * gseg + 6u] = tw.y;
+	}
+	return make_uint2(sum, tw.x);
+}
+
+// The whole look-back where nothing is fetched ahead: the scalar first
+// window for sif >= AIRS_LB_SCALAR_N, the vector one for the segments before.
+// (Two tests and not if/else: the compiler lays rice_kernel out differently
+// for the other form, 15 instructions and two spills fewer, which no
+// measurement covers yet.)
+__device__ __forceinline__ uint2 lb_lookback(const KArgs &a, uint32_t gseg, uint32_t sif, uint32_t lane)
+{
+	LbWin w = {0ull, 0ull};
+	bool have = false;
+	if (sif >= AIRS_LB_SCALAR_N) {
+		w = lb_scalar(a, gseg, lane, 0ull);
+		have = true;
+	}
+	if (!have)
+		w = lb_prefetch(a, gseg, gseg - sif, lane);
+	return lb_resolve(a, gseg, sif, lane, w.gv, w.tv, 1u);
 }
 
 // all-ones when q > 16 (q < 2^16)

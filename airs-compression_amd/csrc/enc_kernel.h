@@ -541,36 +541,13 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 			s_wsum[c][wid] = inc[c];
 	}
 
-	// ---- the segment's last 32 bits (wave 3 rebuilds its last chunk) ------
-#ifndef AIRS_LB_WIN
-#define AIRS_LB_WIN 1
-#endif
-	// look-back windows of 64 granules fetched per round.  A stream is one
-	// frame with ~1024 segments in flight (not ~64); it used four windows
-	// (256 segments back per round), but one window is 12 % faster on the
-	// 64 Mi-sample stream (cold A/B on one box: 64.9 vs 73.5-74.5 us,
-	// DESIGN.md 3.1.2): the extra windows only add loads to the round
-#ifndef AIRS_STREAM_LB_WIN
-#define AIRS_STREAM_LB_WIN 1
-#endif
-	constexpr int LB_WIN = STREAM ? AIRS_STREAM_LB_WIN : AIRS_LB_WIN;
-	// Scalar look-back (experiment, AIRS_SLB=1): the first round reads the
-	// 16 newest granules and the tail through the scalar cache path (glc:
-	// no scalar-cache hit) when the look-back starts, instead of vector loads
-	// issued a chunk earlier that queue behind the CU's cold sample loads.
-	// A stale or unpublished granule only means another round (vector).
-#ifndef AIRS_SLB
-#define AIRS_SLB 1
-#endif
-#ifndef AIRS_SLB_N
-#define AIRS_SLB_N 16
-#endif
-	constexpr bool SLB = AIRS_SLB && LBC >= 1 && !AUTOK;
-	constexpr uint32_t SLB_N = AIRS_SLB_N; // 8, 16 or 32 granules
-	uint64_t gv[LB_WIN];
-#pragma unroll
-	for (int w = 0; w < LB_WIN; w++)
-		gv[w] = 0;
+	// The look-back's first window (wave 0; enc_common.h, DESIGN.md 3.1 step
+	// 4), one window of 64 granules for frames and streams alike.  Where the
+	// look-back overlaps the packing (LBC >= 1), segments with sif >=
+	// AIRS_LB_SCALAR_N read it through scalar loads when the look-back starts
+	// (lb_scalar), instead of vector loads issued a chunk earlier (lb_prefetch)
+	// that queue behind the CU's cold sample loads.
+	LbWin lbw = {0ull, 0ull};
 	__syncthreads(); // B1: wave totals visible
 	uint32_t excl[CH], tot[CH], base[CH];
 	uint32_t A = 0u;
@@ -589,19 +566,16 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 		A += tt;
 	}
 	const uint32_t first_seg = gseg - sif;
-	uint64_t tv0 = 0; // predecessor's tail granule, fetched early (lane 0 of wave 0)
 	if (wid == 0) {
 		if (lane == 0 && !AUTOK) {
 			const uint64_t tag = ((uint64_t)a.epoch << 1) | (is_first ? 1u : 0u);
 			gran_store(&a.agg[gseg], (tag << 32) | (is_first ? HDR_BITS + A : A));
 		}
 		dbg_stamp(a, gseg, 1);
-		if (LBC == 0 && !is_first && !(DBG(2u)) && !AUTOK) {
-			// the first round's windows, newest first: with ~64 segments of a
-			// frame in flight the nearest inclusive prefix is often past 64
-			lb_prefetch<LB_WIN>(a, gv, tv0, gseg, first_seg, lane);
-		}
+		if (LBC == 0 && !is_first && !(DBG(2u)) && !AUTOK)
+			lbw = lb_prefetch(a, gseg, first_seg, lane);
 	}
+	// ---- the segment's last 32 bits (wave 3 rebuilds its last chunk) ------
 	if (!is_last && wid == EWG / 64 - 1 && !(DBG(8u))) {
 		// the last lanes' streams (>= EPT bits each) combined: lane 63 gets
 		// the chunk's last 32 bits
@@ -756,14 +730,11 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 				Lc[i] = 0u;
 			__syncthreads();
 		}
-#ifndef AIRS_LBP
-#define AIRS_LBP LBC
-#endif
-		if (LBC >= 1 && c == (AIRS_LBP) && wid == 0 && !is_first && !(DBG(2u))) {
+		if (LBC >= 1 && c == LBC && wid == 0 && !is_first && !(DBG(2u))) {
 			if (AUTOK) // only the predecessor's tail: the offset is known
-				tv0 = gran_load(&a.tail[gseg - 1u]);
-			else if (!SLB || sif < SLB_N)
-				lb_prefetch<LB_WIN>(a, gv, tv0, gseg, first_seg, lane);
+				lbw.tv = gran_load(&a.tail[gseg - 1u]);
+			else if (sif < AIRS_LB_SCALAR_N) // (the later segments: lb_scalar, below)
+				lbw = lb_prefetch(a, gseg, first_seg, lane);
 		}
 		uint32_t ln[NPIECE][EPT]; // piece lengths (kept for the MODEL fail_bit check)
 		{
@@ -858,164 +829,33 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 		if (c == LBC) {
 			// ---- decoupled look-back (wave 0), overlapped with the packing ----
 			if (wid == 0) {
-#ifdef AIRS_PRIO_LB // experiment: issue priority of the look-back wave
-				__builtin_amdgcn_s_setprio(AIRS_PRIO_LB);
-#endif
 				dbg_stamp(a, gseg, 3);
-				uint32_t Pw = HDR_BITS;
-				if (AUTOK) {
+				uint32_t Pw = HDR_BITS, pred = 0u;
+				if (AUTOK)
 					Pw = auto_P; // from the Rice candidates of the frame
-				} else if (DBG(2u)) {
+				else if (DBG(2u))
 					Pw = HDR_BITS + sif * 37u; // ablation: no look-back (output garbage)
-				} else if (!is_first) {
-					// round 0 uses the granules fetched before packing; every
-					// round covers LB_WIN windows of 64, newest first
-					const bool slb = SLB && sif >= SLB_N;
-					if (slb) {
-						typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-						// (the addresses in SGPRs: uniform, but not known to be)
-						auto sptr = [](const uint64_t *p) {
-							const uint64_t v = (uint64_t)(uintptr_t)p;
-							const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)v);
-							const uint32_t h = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-							return (const uint64_t *)(uintptr_t)(((uint64_t)h << 32) | l);
-						};
-						const uint64_t *gp = sptr(&a.agg[gseg - SLB_N]);
-						const uint64_t *tp = sptr(&a.tail[gseg - 1u]);
-						// q[b] = granules gseg - SLB_N + 8 b .. + 7; the loads and their
-						// wait in one statement (lgkmcnt also counts LDS operations)
-						u32x16 q[SLB_N / 8u];
-						uint64_t tq;
-						if constexpr (SLB_N == 32u)
-							asm volatile("s_load_dwordx16 %0, %5, 0x0 glc\n\t"
-								     "s_load_dwordx16 %1, %5, 0x40 glc\n\t"
-								     "s_load_dwordx16 %2, %5, 0x80 glc\n\t"
-								     "s_load_dwordx16 %3, %5, 0xc0 glc\n\t"
-								     "s_load_dwordx2 %4, %6, 0x0 glc\n\t"
-								     "s_waitcnt lgkmcnt(0)"
-								     : "=&s"(q[0]), "=&s"(q[1]), "=&s"(q[2]), "=&s"(q[3]), "=&s"(tq)
-								     : "s"(gp), "s"(tp)
-								     : "memory");
-						else if constexpr (SLB_N == 8u)
-							asm volatile("s_load_dwordx16 %0, %2, 0x0 glc\n\t"
-								     "s_load_dwordx2 %1, %3, 0x0 glc\n\t"
-								     "s_waitcnt lgkmcnt(0)"
-								     : "=&s"(q[0]), "=&s"(tq)
-								     : "s"(gp), "s"(tp)
-								     : "memory");
-						else
-							asm volatile("s_load_dwordx16 %0, %3, 0x0 glc\n\t"
-								     "s_load_dwordx16 %1, %3, 0x40 glc\n\t"
-								     "s_load_dwordx2 %2, %4, 0x0 glc\n\t"
-								     "s_waitcnt lgkmcnt(0)"
-								     : "=&s"(q[0]), "=&s"(q[1]), "=&s"(tq)
-								     : "s"(gp), "s"(tp)
-								     : "memory");
-						// granule gseg - SLB_N + i -> lane SLB_N - 1 - i; lanes >= SLB_N read
-						// as unpublished (tag 0): they send the round to the vector path
-						// unless an inclusive granule comes first
-						uint32_t vl = 0u, vh = 0u;
-#pragma unroll
-						for (uint32_t i = 0; i < SLB_N; i++) {
-							vl = lane == SLB_N - 1u - i ? q[i >> 3][2u * (i & 7u)] : vl;
-							vh = lane == SLB_N - 1u - i ? q[i >> 3][2u * (i & 7u) + 1u] : vh;
-						}
-						gv[0] = ((uint64_t)vh << 32) | vl;
-						tv0 = tq;
-					}
-					uint32_t sum = 0u, spins = 0u, lb_rounds = 0u;
-					int64_t j = (int64_t)gseg - 1;
-					int nwin = slb ? 1 : LB_WIN; // the scalar round fills one window
-					bool done = false;
-					while (!done) {
-						lb_rounds++;
-						bool retry = false;
-#pragma unroll
-						for (int w = 0; w < LB_WIN; w++) {
-							if (w >= nwin || done || retry)
-								break;
-							const int64_t idx = j - 64 * w - (int64_t)lane;
-							const bool inr = idx >= (int64_t)first_seg;
-							const uint32_t tag = (uint32_t)(gv[w] >> 32);
-							const bool valid = inr && (tag >> 1) == a.epoch;
-							const bool incl = valid && (tag & 1u);
-							const uint64_t incl_m = __ballot(incl);
-							const uint64_t bad_m = __ballot(inr && !valid);
-							const uint32_t fi =
-								incl_m ? (uint32_t)__ffsll((unsigned long long)incl_m) - 1u : 64u;
-							const uint64_t need = fi >= 63u ? ~0ull : ((2ull << fi) - 1ull);
-							if (bad_m & need) {
-								// a needed predecessor has not published: re-poll from here
-								j -= 64 * w;
-								retry = true;
-								break;
-							}
-							sum += wave_sum((inr && lane <= fi) ? (uint32_t)gv[w] : 0u);
-							if (incl_m)
-								done = true;
-						}
-						if (done)
-							break;
-						if (retry) {
-							if (++spins > AIRS_SPIN_LIMIT) {
-								// never expected: a predecessor did not publish.  Give up
-								// (output is garbage, the host reports the fault counter)
-								if (lane == 0)
-									atomicAdd(a.ticket + AIRS_FAULT_WORD, 1u);
-								break;
-							}
-							__builtin_amdgcn_s_sleep(1);
-						} else {
-							j -= 64 * nwin;
-						}
-						nwin = LB_WIN;
-#pragma unroll
-						for (int w = 0; w < LB_WIN; w++) {
-							const int64_t idx = j - 64 * w - (int64_t)lane;
-							gv[w] = idx >= (int64_t)first_seg ? gran_load(&a.agg[idx]) : 0ull;
-						}
-					}
-					Pw = sum;
+				if (is_first || (DBG(2u))) {
+					// header bytes 20-21 (low half of the outlier field) share
+					// the first payload dword of a 22-byte header
+					pred = (EXT_HDR && ENC != ENC_RAW && !STREAM) ? (cd.outlier & 0xFFFFu) : 0u;
+				} else if (AUTOK) {
+					pred = lb_tail_wait(a, gseg, lane, lbw.tv).x;
+				} else {
+					// the window fetched before the packing, or the scalar one now
+					if (LBC >= 1 && sif >= AIRS_LB_SCALAR_N)
+						lbw = lb_scalar(a, gseg, lane, 0ull);
+					const uint2 pp = lb_resolve(a, gseg, sif, lane, lbw.gv, lbw.tv, 1u);
+					Pw = pp.x;
+					pred = pp.y;
 					if (lane == 0)
 						gran_store(&a.agg[gseg], ((((uint64_t)a.epoch << 1) | 1u) << 32) | (Pw + A));
-					if ((DBG(65536u)) && a.dbgts && lane == 0)
-						a.dbgts[8u * gseg + 5u] = ((uint64_t)spins << 32) | lb_rounds;
-					if ((DBG(256u)) && lane == 0) { // look-back statistics (debug)
-						atomicAdd(a.ticket + 20, 1u);
-						atomicAdd(a.ticket + 21, lb_rounds);
-						atomicAdd(a.ticket + 22, spins);
-					}
 				}
 				if (lane == 0) {
-					uint32_t pred = 0u;
-					if (is_first || (DBG(2u))) {
-						// header bytes 20-21 (low half of the outlier field) share
-						// the first payload dword of a 22-byte header
-						pred = (EXT_HDR && ENC != ENC_RAW && !STREAM) ? (cd.outlier & 0xFFFFu) : 0u;
-					} else {
-						uint64_t tv = tv0;
-						uint32_t spins = 0;
-						for (; (uint32_t)(tv >> 32) != a.epoch; spins++) {
-							if (spins > AIRS_SPIN_LIMIT) {
-								atomicAdd(a.ticket + AIRS_FAULT_WORD, 1u);
-								break;
-							}
-							__builtin_amdgcn_s_sleep(1);
-							tv = gran_load(&a.tail[gseg - 1u]);
-							if (DBG(256u))
-								atomicAdd(a.ticket + 23, 1u);
-						}
-						if ((DBG(65536u)) && a.dbgts && !AUTOK)
-							a.dbgts[8u * gseg + 6u] = spins;
-						pred = (uint32_t)tv;
-					}
 					s_misc[1] = Pw;
 					s_misc[2] = pred;
 				}
 				dbg_stamp(a, gseg, 2);
-#ifdef AIRS_PRIO_LB
-				__builtin_amdgcn_s_setprio(AIRS_PRIO_P2);
-#endif
 			}
 			__syncthreads();
 			P = __builtin_amdgcn_readfirstlane(s_misc[1]);

@@ -38,8 +38,9 @@
 // escape next to a long code) keeps its mapped values in V; the packer
 // re-codes it from the table in a wave-uniform slow step.
 //
-// Look-back granules, frame-interleaved dispatch, the tail granule and the
-// bounded spins are those of encode_kernel.
+// Frame-interleaved dispatch, the granules and the look-back itself (the lb_*
+// functions of enc_common.h, bounded spins included) are those of
+// encode_kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -75,9 +76,6 @@ namespace airs {
 #endif
 #ifndef AIRS_RICE_LBC // the look-back is evaluated after packing this many chunks (wave 0)
 #define AIRS_RICE_LBC 4
-#endif
-#ifndef AIRS_RICE_SLB // granules of the scalar first look-back round (16 or 32)
-#define AIRS_RICE_SLB 16
 #endif
 // cache policy of the payload stores (gfx950 aux: 2 = nt): the output is
 // written once and not read back by this kernel (round 6: a 128 MiB read +
@@ -186,128 +184,6 @@ __device__ __forceinline__ void pack_chunk(RPack &p, const uint32_t (&V)[8], con
 	}
 }
 
-// Evaluate a look-back from a first window (gv: granule gseg - 1 - lane,
-// newest first; tv: the predecessor's tail granule), reloading with vector
-// loads until the segment's frame bit offset is known: (offset, the
-// predecessor's last 32 bits).  Every published granule stays true, so the
-// first window may be of any age.
-__device__ __forceinline__ uint2 lb_resolve(const KArgs &a, uint32_t gseg, uint32_t sif, uint32_t lane, uint64_t gv,
-					    uint64_t tv, uint32_t rounds)
-{
-	const uint32_t first_seg = gseg - sif;
-	uint32_t sum = 0u, spins = 0u;
-	int64_t j = (int64_t)gseg - 1;
-	for (;;) {
-		const int64_t idx = j - (int64_t)lane;
-		const bool inr = idx >= (int64_t)first_seg;
-		const uint32_t tag = (uint32_t)(gv >> 32);
-		const bool valid = inr && (tag >> 1) == a.epoch;
-		const bool incl = valid && (tag & 1u);
-		const uint64_t incl_m = __ballot(incl);
-		const uint64_t bad_m = __ballot(inr && !valid);
-		const uint32_t fi = incl_m ? (uint32_t)__ffsll((unsigned long long)incl_m) - 1u : 64u;
-		const uint64_t need = fi >= 63u ? ~0ull : ((2ull << fi) - 1ull);
-		if (!(bad_m & need)) {
-			sum += wave_sum((inr && lane <= fi) ? (uint32_t)gv : 0u);
-			if (incl_m)
-				break;
-			j -= 64; // every granule of this window is an aggregate: the next window
-			rounds++;
-		} else if (++spins > AIRS_SPIN_LIMIT) {
-			if (lane == 0)
-				atomicAdd(a.ticket + AIRS_FAULT_WORD, 1u); // never expected (the host reports it)
-			break;
-		} else {
-			__builtin_amdgcn_s_sleep(1); // a needed predecessor has not published: re-poll
-			rounds++;
-		}
-		const int64_t nidx = j - (int64_t)lane;
-		gv = gran_load(&a.agg[nidx >= (int64_t)first_seg ? nidx : (int64_t)first_seg]);
-	}
-	// the predecessor's tail (lane 0's copy is the one used)
-	uint32_t s2 = 0;
-	for (; (uint32_t)(tv >> 32) != a.epoch; s2++) {
-		if (s2 > AIRS_SPIN_LIMIT) {
-			if (lane == 0)
-				atomicAdd(a.ticket + AIRS_FAULT_WORD, 1u);
-			break;
-		}
-		__builtin_amdgcn_s_sleep(1);
-		tv = gran_load(&a.tail[gseg - 1u]);
-	}
-	if (DBG(65536u) && !DBG(262144u) && a.dbgts && lane == 0) {
-		a.dbgts[8u * gseg + 5u] = ((uint64_t)spins << 32) | rounds;
-		a.dbgts[8u * gseg + 6u] = s2;
-	}
-	return make_uint2(sum, (uint32_t)tv);
-}
-
-// The look-back (wave 0): the segment's frame bit
-// offset P (header bits included) and the predecessor's last 32 bits.  The
-// first round reads the 16 newest granules and the tail through scalar loads
-// (one asm statement with its wait: no register of an outstanding load is
-// visible to the compiler); further rounds are vector loads of
-// 64 granules, newest first.  Not for the frame's first segment.
-__device__ __forceinline__ uint2 rice_lookback(const KArgs &a, uint32_t gseg, uint32_t sif, uint32_t lane,
-					       uint64_t gearly)
-{
-	uint32_t rounds = 1u;
-	constexpr uint32_t SLB_N = AIRS_RICE_SLB;
-	const uint32_t first_seg = gseg - sif;
-	uint64_t gv = 0ull, tv = 0ull;
-	bool have = false;
-	if (sif >= SLB_N) {
-		typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-		auto sptr = [](const uint64_t *p) {
-			const uint64_t v = (uint64_t)(uintptr_t)p;
-			const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)v);
-			const uint32_t h = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-			return (const uint64_t *)(uintptr_t)(((uint64_t)h << 32) | l);
-		};
-		const uint64_t *gp = sptr(&a.agg[gseg - SLB_N]);
-		const uint64_t *tp = sptr(&a.tail[gseg - 1u]);
-		// q[b]: granules gseg - SLB_N + 8 b .. + 7 -> lanes SLB_N - 1 - (8 b + i);
-		// lanes >= SLB_N read as unpublished
-		u32x16 q[SLB_N / 8u];
-		uint64_t tq;
-		if constexpr (SLB_N == 32u)
-			asm volatile("s_load_dwordx16 %0, %5, 0x0 glc\n\t"
-				     "s_load_dwordx16 %1, %5, 0x40 glc\n\t"
-				     "s_load_dwordx16 %2, %5, 0x80 glc\n\t"
-				     "s_load_dwordx16 %3, %5, 0xc0 glc\n\t"
-				     "s_load_dwordx2 %4, %6, 0x0 glc\n\t"
-				     "s_waitcnt lgkmcnt(0)"
-				     : "=&s"(q[0]), "=&s"(q[1]), "=&s"(q[2]), "=&s"(q[3]), "=&s"(tq)
-				     : "s"(gp), "s"(tp)
-				     : "memory");
-		else
-			asm volatile("s_load_dwordx16 %0, %3, 0x0 glc\n\t"
-				     "s_load_dwordx16 %1, %3, 0x40 glc\n\t"
-				     "s_load_dwordx2 %2, %4, 0x0 glc\n\t"
-				     "s_waitcnt lgkmcnt(0)"
-				     : "=&s"(q[0]), "=&s"(q[1]), "=&s"(tq)
-				     : "s"(gp), "s"(tp)
-				     : "memory");
-		// lanes >= SLB_N: the window read when the aggregate was published
-		// (granules gseg - 1 - lane; any published value stays true)
-		uint32_t vl = (uint32_t)gearly, vh = (uint32_t)(gearly >> 32);
-#pragma unroll
-		for (uint32_t i = 0; i < SLB_N; i++) {
-			vl = lane == SLB_N - 1u - i ? q[i >> 3][2u * (i & 7u)] : vl;
-			vh = lane == SLB_N - 1u - i ? q[i >> 3][2u * (i & 7u) + 1u] : vh;
-		}
-		gv = ((uint64_t)vh << 32) | vl;
-		tv = tq;
-		have = true;
-	}
-	if (!have) {
-		const int64_t idx = (int64_t)gseg - 1 - (int64_t)lane;
-		gv = gran_load(&a.agg[idx >= (int64_t)first_seg ? idx : (int64_t)first_seg]);
-		tv = gran_load(&a.tail[gseg - 1u]);
-	}
-	return lb_resolve(a, gseg, sif, lane, gv, tv, rounds);
-}
-
 // The look-back on scalar loads only (lbmode bit 0: a frame's segments all
 // run on one XCD, so its L2 holds every granule the frame's segments write
 // and a scalar load that misses the scalar cache sees the newest value).
@@ -333,22 +209,16 @@ __device__ __forceinline__ uint2 rice_lookback_s(const KArgs &a, uint32_t gseg, 
 	// of 8 granules, newest first: the older half is loaded only when the
 	// newer one holds aggregates alone.
 	constexpr uint32_t SW = (AIRS_RICE_FW & 2) ? 8u : AIRS_RICE_SWIN;
-	auto sptr = [](const uint64_t *p) {
-		const uint64_t v = (uint64_t)(uintptr_t)p;
-		const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)v);
-		const uint32_t h = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-		return (const uint64_t *)(uintptr_t)(((uint64_t)h << 32) | l);
-	};
 	const uint32_t first_seg = gseg - sif, epoch = a.epoch;
 	uint32_t sum = 0u, polls = 0u, rounds = 0u, j = gseg - 1u;
 	uint64_t tv = 0ull;
 	bool have_tail = false, done = false;
 	while (polls < AIRS_RICE_SPOLL) {
 		const uint32_t base = j >= first_seg + (SW - 1u) ? j - (SW - 1u) : first_seg;
-		const uint64_t *gp = sptr(&a.agg[base]);
+		const uint64_t *gp = lb_sptr(&a.agg[base]);
 		u32x16 q[SW / 8u];
 		if (!have_tail) {
-			const uint64_t *tp = sptr(&a.tail[gseg - 1u]);
+			const uint64_t *tp = lb_sptr(&a.tail[gseg - 1u]);
 			if constexpr (SW == 16u)
 				asm volatile("s_load_dwordx16 %0, %3, 0x0 glc\n\t"
 					     "s_load_dwordx16 %1, %3, 0x40 glc\n\t"
@@ -412,7 +282,7 @@ __device__ __forceinline__ uint2 rice_lookback_s(const KArgs &a, uint32_t gseg, 
 	}
 	// the predecessor's tail
 	while (done && !have_tail && polls < AIRS_RICE_SPOLL) {
-		const uint64_t *tp = sptr(&a.tail[gseg - 1u]);
+		const uint64_t *tp = lb_sptr(&a.tail[gseg - 1u]);
 		polls++;
 		__builtin_amdgcn_s_sleep(1);
 		asm volatile("s_load_dwordx2 %0, %1, 0x0 glc\n\t"
@@ -478,23 +348,6 @@ __device__ __forceinline__ void rice_store(const uint32_t *Lx, uint32_t Pc, uint
 			if (4u * gw + b < cap)
 				fdst[4u * gw + b] = (uint8_t)(v >> (24u - 8u * b));
 	}
-}
-
-// AUTO: the predecessor's last 32 bits (its tail granule, published once it
-// knows the frame's k), polled by wave 0 (bounded as every wait)
-__device__ __forceinline__ uint32_t rice_tail_wait(const KArgs &a, uint32_t gseg)
-{
-	uint64_t tv = gran_load(&a.tail[gseg - 1u]);
-	for (uint32_t s2 = 0; (uint32_t)(tv >> 32) != a.epoch; s2++) {
-		if (s2 > AIRS_SPIN_LIMIT) {
-			if ((threadIdx.x & 63u) == 0)
-				atomicAdd(a.ticket + AIRS_FAULT_WORD, 1u);
-			break;
-		}
-		__builtin_amdgcn_s_sleep(1);
-		tv = gran_load(&a.tail[gseg - 1u]);
-	}
-	return (uint32_t)tv;
 }
 
 // AUTO (CMP_GPU_AUTO_RICE, fused): the frame's k and this segment's payload
@@ -1078,10 +931,11 @@ rice_kernel(KArgs a_in)
 				if (DBG(2u)) // ablation: no look-back (offsets invented, output garbage)
 					pp = make_uint2(HDR_BITS + sif * 37u, 0u);
 				else if (AUTO)
-					pp = make_uint2(auto_P, is_first ? hdr_pred : rice_tail_wait(a, gseg));
+					pp = make_uint2(auto_P, is_first ? hdr_pred
+									 : lb_tail_wait(a, gseg, lane, gran_load(&a.tail[gseg - 1u])).x);
 				else if (!is_first)
 					pp = (a.lbmode & 1u) && sif >= 16u ? rice_lookback_s(a, gseg, sif, lane)
-									     : rice_lookback(a, gseg, sif, lane, 0ull);
+									     : lb_lookback(a, gseg, sif, lane);
 				if (lane == 0) {
 					if (!AUTO && !is_first)
 						gran_store(&a.agg[gseg], ((((uint64_t)a.epoch << 1) | 1u) << 32) | (pp.x + A));
@@ -1111,10 +965,11 @@ rice_kernel(KArgs a_in)
 		if (wid == 0) {
 			uint2 pp = make_uint2(HDR_BITS, hdr_pred);
 			if (AUTO)
-				pp = make_uint2(auto_P, is_first ? hdr_pred : rice_tail_wait(a, gseg));
+				pp = make_uint2(auto_P, is_first ? hdr_pred
+								 : lb_tail_wait(a, gseg, lane, gran_load(&a.tail[gseg - 1u])).x);
 			else if (!is_first)
 				pp = (a.lbmode & 1u) && sif >= 16u ? rice_lookback_s(a, gseg, sif, lane)
-								     : rice_lookback(a, gseg, sif, lane, 0ull);
+								     : lb_lookback(a, gseg, sif, lane);
 			if (lane == 0) {
 				if (!AUTO && !is_first)
 					gran_store(&a.agg[gseg], ((((uint64_t)a.epoch << 1) | 1u) << 32) | (pp.x + A));

@@ -7,7 +7,7 @@
 // bitstream_writer.h:124-158, bitstream_flush :205-227), over up to
 // AIRS_STREAM_MAX samples.  Its segments form ONE look-back chain (16 Ki
 // segments for 256 Mi samples); its look-back reads one window of 64
-// granules per round, like a frame's (AIRS_STREAM_LB_WIN, enc_kernel.h).
+// granules per round, like a frame's (lb_resolve, enc_common.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

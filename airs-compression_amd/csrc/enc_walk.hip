@@ -735,6 +735,7 @@ __global__ __launch_bounds__(320) void walk_kernel(WArgs a)
 					const uint32_t enc = prim_st ? ENC_P : ENC_S;
 					pred = (enc != ENC_RAW) ? ((prim_st ? cp.outlier : cs.outlier) & 0xFFFFu) : 0u;
 				} else {
+					// (mirrors lb_resolve and lb_tail_wait of enc_common.h, on WArgs)
 					const uint64_t first_seg = gseg - j;
 					uint32_t sum = 0u, spins = 0u;
 					int64_t jj = (int64_t)gseg - 1;

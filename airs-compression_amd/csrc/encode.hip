@@ -2409,13 +2409,6 @@ static uint32_t sync_wait(struct airs_dev_engine *e, bool waited)
 		if (f)
 			fclose(f);
 	}
-	if (g_dbg & 256) {
-		uint32_t st[4];
-		HIPCHECK(hipMemcpy(st, e->ticket + 20, sizeof(st), hipMemcpyDeviceToHost));
-		fprintf(stderr, "airscmp look-back stats: lookbacks=%u rounds=%u retries=%u tail_repolls=%u\n", st[0],
-			st[1], st[2], st[3]);
-		(void)hipMemset(e->ticket + 20, 0, sizeof(st));
-	}
 #endif
 	if (faults) {
 		snprintf(g_err, sizeof(g_err), "%u look-back give-ups", faults);
