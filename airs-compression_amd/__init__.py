@@ -29,6 +29,9 @@ GATHER_PATCH_IDS = 0x1  # CMP_GPU_GATHER_PATCH_IDS
 OPT_EXCLUSIVE = 1  # cmp_gpu_engine_set_option (include/cmp_gpu.h)
 OPT_WALK_SEGMENT = 2
 OPT_NO_CONTEXT_WALK = 3
+OPT_IMAGE_CHUNK = 4  # CMP_GPU_OPT_IMAGE_CHUNK: bytes of staging per chunk of decompress_image (0: 256 MiB)
+IMG_MODEL_IN = 0x1  # CMP_GPU_IMG_MODEL_IN (cmp_gpu_decompress_image)
+IMG_BIG_ENDIAN = 0x2  # CMP_GPU_IMG_BIG_ENDIAN
 KIND_TO_GPU = {"u16": GPU_U16, "i16": GPU_I16, "i16_in_i32": GPU_I16_IN_I32}
 
 
@@ -114,6 +117,26 @@ class GpuDecodeSeqBatch(ctypes.Structure):
     ]
 
 
+class GpuDecodeImage(ctypes.Structure):
+    """struct cmp_gpu_decode_image (include/cmp_gpu.h)."""
+    _fields_ = [
+        ("type", c_int),
+        ("src", c_void_p),
+        ("src_size", c_uint64),
+        ("offsets", c_void_p),
+        ("num_frames", c_uint32),
+        ("dst", c_void_p),
+        ("dst_capacity", c_uint64),
+        ("dst_offsets", c_void_p),
+        ("status", c_void_p),
+        ("checksum_ok", c_void_p),
+        ("model", c_void_p),
+        ("model_samples", c_uint32),
+        ("model_n", c_void_p),
+        ("flags", c_uint32),
+    ]
+
+
 class AirsLib(CmpLib):
     """CmpLib plus the cmp_gpu.h device batch API."""
 
@@ -154,6 +177,10 @@ class AirsLib(CmpLib):
         L.cmp_gpu_gather_plan.argtypes = [c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint64, c_void_p,
                                           c_void_p, c_void_p, c_void_p]
         L.cmp_gpu_gather_plan.restype = c_uint32
+        L.cmp_gpu_decompress_image.argtypes = [c_void_p, POINTER(GpuDecodeImage)]
+        L.cmp_gpu_decompress_image.restype = c_uint32
+        L.cmp_gpu_frame_table.argtypes = [c_void_p, c_uint64, c_void_p, c_uint64, POINTER(c_uint64)]
+        L.cmp_gpu_frame_table.restype = c_uint64
 
     def gpu_available(self) -> bool:
         return bool(self.lib.cmp_gpu_available())
@@ -175,6 +202,22 @@ class AirsLib(CmpLib):
                                          offs.ctypes.data, sz.ctypes.data, ids.ctypes.data if want_ids else None)
         return int(r), rb, offs[:n], sz[:n], (ids[:n] if want_ids else None)
 
+    def frame_table(self, image, max_frames: int | None = None):
+        """cmp_gpu_frame_table on a host image (bytes-like) of back-to-back frames
+        (no device).  Returns (count, offsets, bad_at): the frames found, the
+        uint64 offsets written (all of them, or the first max_frames) and the
+        byte where the walk stopped short, or None when the image ends at a
+        frame's end."""
+        import numpy as np
+        img = np.frombuffer(image, dtype=np.uint8)
+        bad = c_uint64(0)
+        ptr = img.ctypes.data if img.size else None
+        count = int(self.lib.cmp_gpu_frame_table(ptr, img.size, None, 0, ctypes.byref(bad)))
+        room = count if max_frames is None else max_frames
+        offs = np.zeros(max(room, 1), dtype=np.uint64)
+        self.lib.cmp_gpu_frame_table(ptr, img.size, offs.ctypes.data, room, ctypes.byref(bad))
+        return count, offs[:min(room, count)], (None if bad.value == 2 ** 64 - 1 else int(bad.value))
+
     def engine(self, stream: int | None = None) -> "GpuEngine":
         return GpuEngine(self, stream)
 
@@ -192,7 +235,7 @@ class GpuEngine:
         self.handle = h
 
     def set_option(self, option: int, value: int) -> int:
-        """cmp_gpu_engine_set_option (OPT_EXCLUSIVE, OPT_WALK_SEGMENT, OPT_NO_CONTEXT_WALK)."""
+        """cmp_gpu_engine_set_option (OPT_EXCLUSIVE, OPT_WALK_SEGMENT, OPT_NO_CONTEXT_WALK, OPT_IMAGE_CHUNK)."""
         return int(self.lib.lib.cmp_gpu_engine_set_option(self.handle, option, value))
 
     def close(self):
@@ -241,6 +284,24 @@ class GpuEngine:
                               status=status_ptr or None, model=model_ptr or None, model_stride=model_stride,
                               model_n=model_n_ptr or None, checksum_ok=checksum_ok_ptr or None, flags=flags)
         return self.lib.lib.cmp_gpu_decompress_sequences(self.handle, ctypes.byref(b))
+
+    def decompress_image(self, kind: str, src_ptr: int, src_size: int, offsets, dst_ptr: int, dst_capacity: int,
+                         status_ptr: int, checksum_ok_ptr: int = 0, model_ptr: int = 0, model_samples: int = 0,
+                         model_n_ptr: int = 0, flags: int = 0):
+        """cmp_gpu_decompress_image: the frames at src + offsets[f] (host table,
+        any alignment) decoded as one context into samples packed back to back
+        at dst (flags: IMG_MODEL_IN, IMG_BIG_ENDIAN).  Returns (rc, dst_offsets):
+        the host uint64 array [num_frames + 1] of each frame's byte offset in dst."""
+        import numpy as np
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        dof = np.zeros(offs.size + 1, dtype=np.uint64)
+        b = GpuDecodeImage(type=KIND_TO_GPU[kind], src=src_ptr or None, src_size=src_size,
+                           offsets=offs.ctypes.data, num_frames=offs.size, dst=dst_ptr or None,
+                           dst_capacity=dst_capacity, dst_offsets=dof.ctypes.data, status=status_ptr or None,
+                           checksum_ok=checksum_ok_ptr or None, model=model_ptr or None,
+                           model_samples=model_samples, model_n=model_n_ptr or None, flags=flags)
+        r = self.lib.lib.cmp_gpu_decompress_image(self.handle, ctypes.byref(b))
+        return int(r), dof
 
     def encode_stream(self, kind: str, src_ptr: int, num_samples: int, preprocessing: int, encoder_type: int,
                       encoder_param: int, encoder_outlier: int, dst_ptr: int, dst_capacity: int,

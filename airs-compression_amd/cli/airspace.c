@@ -23,10 +23,11 @@
  * Decompression (the reference's default mode prints "Decompression not
  * implemented yet", airspacecli.c:421-423) is an extension here: the frames
  * of each .air input are decoded on the GPU and written back as big-endian
- * 16-bit samples.  Each chunk of frames (up to BATCH_BYTES), MODEL frames
- * included, is one cmp_gpu_decompress_sequences() call: the model is rebuilt
- * on the device and carried from chunk to chunk there, and every frame that
- * has a checksum is verified against it.
+ * 16-bit samples.  The file goes to the device as it is and is one
+ * cmp_gpu_decompress_image() call over the table of cmp_gpu_frame_table():
+ * MODEL frames included (the model is rebuilt on the device), the samples come
+ * back big-endian and packed, and every frame that has a checksum is verified
+ * against it.
  */
 #include <errno.h>
 #include <getopt.h>
@@ -579,156 +580,89 @@ static uint32_t be24(const uint8_t *p)
 
 static int decompress_file(struct job *j, struct dev *d, int fi)
 {
-	uint8_t *raw, *out = NULL;
-	size_t size, pos, total = 0, model_cap = 0;
+	uint8_t *raw, *out = NULL, *ck;
+	uint64_t *offs = NULL, *dof, nf, bad, f;
+	uint32_t *st = NULL, e;
+	size_t size, total = 0;
 	int owned, r = -1;
-	void *d_model = NULL, *d_model_n = NULL;
 
 	if (load_file(j->in[fi], &raw, &size, &owned))
 		return -1;
-	/* walk the frames: compressed size at bytes 2-4, original size at 5-7 */
-	for (pos = 0; pos < size;) {
-		uint32_t fs;
-
-		if (size - pos < HDR_MIN || (fs = be24(raw + pos + 2)) < HDR_MIN || fs > size - pos ||
-		    be24(raw + pos + 5) % 2u) {
-			log_msg(LOG_ERROR, "%s: not a valid AIRSPACE frame at byte %lu", display(j->in[fi]),
-				(unsigned long)pos);
-			goto out;
+	/* the frame table: compressed size at bytes 2-4; original size at 5-7, even */
+	nf = cmp_gpu_frame_table(raw, size, NULL, 0, &bad);
+	offs = xmalloc((size_t)(2u * nf + 1u) * sizeof(*offs));
+	dof = offs + nf;
+	cmp_gpu_frame_table(raw, size, offs, nf, NULL);
+	for (f = 0; f < nf; f++) {
+		if (be24(raw + offs[f] + 5) % 2u) {
+			bad = offs[f];
+			break;
 		}
-		total += be24(raw + pos + 5);
-		pos += fs;
+		total += be24(raw + offs[f] + 5);
+	}
+	if (bad != UINT64_MAX) {
+		log_msg(LOG_ERROR, "%s: not a valid AIRSPACE frame at byte %lu", display(j->in[fi]),
+			(unsigned long)bad);
+		goto out;
 	}
 	out = xmalloc(total);
 	if (dev_open(d))
 		goto out;
-	/* samples of model the context holds (none yet), kept on the device */
-	if (hipMalloc(&d_model_n, 4) != hipSuccess || hipMemset(d_model_n, 0, 4) != hipSuccess)
-		goto gpu_fail;
-	{
-		size_t o = 0;
+	if (nf) {
+		/* the file as it is, one call, the samples as the output file holds them */
+		struct cmp_gpu_decode_image b;
 
-		for (pos = 0; pos < size;) {
-			/* a chunk: consecutive frames, MODEL frames included, decoded as
-			 * one sequence; the model carries on to the next chunk on the device */
-			size_t q = pos, nrun = 0, cap = 24, nmax = 1, dstride, i;
-			struct cmp_gpu_decode_seq_batch b;
-			uint8_t *stage, *ck;
-			uint16_t *x;
-			uint32_t *st, e;
+		if (nf > UINT32_MAX) {
+			log_msg(LOG_ERROR, "%s: too many frames", display(j->in[fi]));
+			goto out;
+		}
+		/* statuses, then one verification byte per frame */
+		if (dev_reserve(&d->src, &d->src_cap, size) || dev_reserve(&d->dst, &d->dst_cap, total + 2u) ||
+		    dev_reserve(&d->sizes, &d->sizes_cap, 5u * (size_t)nf))
+			goto out;
+		if (hipMemcpy(d->src, raw, size, hipMemcpyHostToDevice) != hipSuccess)
+			goto gpu_fail;
+		memset(&b, 0, sizeof(b));
+		b.type = CMP_GPU_U16; /* the reference CLI writes u16 frames only */
+		b.src = d->src;
+		b.src_size = size;
+		b.offsets = offs;
+		b.num_frames = (uint32_t)nf;
+		b.dst = d->dst;
+		b.dst_capacity = total;
+		b.dst_offsets = dof;
+		b.status = d->sizes;
+		b.checksum_ok = (uint8_t *)d->sizes + 4u * (size_t)nf;
+		b.flags = CMP_GPU_IMG_BIG_ENDIAN;
+		e = cmp_gpu_decompress_image(d->eng, &b);
+		if (!cmp_is_error(e))
+			e = cmp_gpu_synchronize(d->eng);
+		if (cmp_is_error(e)) {
+			log_cmp(e, "Decompression failed for %s", display(j->in[fi]));
+			goto out;
+		}
+		st = xmalloc(5u * (size_t)nf);
+		ck = (uint8_t *)st + 4u * (size_t)nf;
+		if (hipMemcpy(st, d->sizes, 5u * (size_t)nf, hipMemcpyDeviceToHost) != hipSuccess ||
+		    (total && hipMemcpy(out, d->dst, total, hipMemcpyDeviceToHost) != hipSuccess))
+			goto gpu_fail;
+		for (f = 0; f < nf; f++) {
+			const uint8_t *h = raw + offs[f];
+			const enum cmp_error code = cmp_get_error_code(st[f]);
 
-			while (q < size) {
-				const uint32_t fs = be24(raw + q + 2), n = be24(raw + q + 5) / 2u;
-				const size_t c = fs < 24u ? 24u : ((size_t)fs + 7u) & ~(size_t)7u;
-				const size_t ncap = c > cap ? c : cap, nn = n > nmax ? n : nmax;
-
-				if (nrun && ((nrun + 1u) * (ncap + 2u * nn + 16u) > BATCH_BYTES || nrun == 65535u))
-					break;
-				cap = ncap;
-				nmax = nn;
-				nrun++;
-				q += fs;
-			}
-			dstride = (2u * nmax + 15u) & ~(size_t)15u; /* 16-byte rows: vector stores */
-			/* statuses, then one verification byte per frame */
-			if (dev_reserve(&d->src, &d->src_cap, nrun * cap) ||
-			    dev_reserve(&d->dst, &d->dst_cap, nrun * dstride) ||
-			    dev_reserve(&d->sizes, &d->sizes_cap, 5u * nrun))
-				goto out;
-			if (nmax > model_cap) { /* a larger model buffer; what it holds moves over */
-				void *m = NULL;
-
-				if (hipMalloc(&m, dstride) != hipSuccess)
-					goto gpu_fail;
-				e = !d_model ||
-				    hipMemcpy(m, d_model, 2u * model_cap, hipMemcpyDeviceToDevice) == hipSuccess;
-				if (d_model)
-					hipFree(d_model);
-				d_model = m;
-				model_cap = nmax;
-				if (!e)
-					goto gpu_fail;
-			}
-			stage = calloc(nrun, cap);
-			if (!stage) {
-				log_errno("Memory allocation failed");
-				goto out;
-			}
-			for (i = 0, q = pos; i < nrun; i++) {
-				const uint32_t fs = be24(raw + q + 2);
-
-				memcpy(stage + i * cap, raw + q, fs);
-				q += fs;
-			}
-			e = hipMemcpy(d->src, stage, nrun * cap, hipMemcpyHostToDevice) == hipSuccess;
-			free(stage);
-			if (!e)
-				goto gpu_fail;
-			memset(&b, 0, sizeof(b));
-			b.type = CMP_GPU_U16; /* the reference CLI writes u16 frames only */
-			b.src = d->src;
-			b.src_stride = cap;
-			b.src_capacity = (uint32_t)cap;
-			b.num_ctx = 1;
-			b.frames_per_ctx = (uint32_t)nrun;
-			b.dst = d->dst;
-			b.dst_stride = dstride;
-			b.dst_samples = (uint32_t)nmax;
-			b.status = d->sizes;
-			b.model = d_model;
-			b.model_stride = dstride;
-			b.model_n = d_model_n;
-			b.checksum_ok = (uint8_t *)d->sizes + 4u * nrun;
-			b.flags = CMP_GPU_SEQ_MODEL_IN;
-			e = cmp_gpu_decompress_sequences(d->eng, &b);
-			if (!cmp_is_error(e))
-				e = cmp_gpu_synchronize(d->eng);
-			if (cmp_is_error(e)) {
-				log_cmp(e, "Decompression failed for %s", display(j->in[fi]));
-				goto out;
-			}
-			st = xmalloc(5u * nrun);
-			ck = (uint8_t *)st + 4u * nrun;
-			x = xmalloc(nrun * dstride);
-			if (hipMemcpy(st, d->sizes, 5u * nrun, hipMemcpyDeviceToHost) != hipSuccess ||
-			    hipMemcpy(x, d->dst, nrun * dstride, hipMemcpyDeviceToHost) != hipSuccess) {
-				free(st);
-				free(x);
-				goto gpu_fail;
-			}
-			for (i = 0; i < nrun; i++) {
-				const uint32_t n = be24(raw + pos + 5) / 2u;
-				const uint16_t *xi = (const uint16_t *)((const uint8_t *)x + i * dstride);
-				const enum cmp_error code = cmp_get_error_code(st[i]);
-				int bad = 1;
-				uint32_t k;
-
-				if ((raw[pos + 15] >> 4) == CMP_PREPROCESS_MODEL &&
-				    (code == CMP_ERR_PARAMS_INVALID || code == CMP_ERR_SRC_SIZE_MISMATCH))
-					log_msg(LOG_ERROR, "%s: MODEL frame without a preceding frame of its size",
-						display(j->in[fi]));
-				else if (cmp_is_error(st[i]) || st[i] != n)
-					log_cmp(cmp_is_error(st[i]) ? st[i] : (uint32_t) - (int32_t)CMP_ERR_INT_BITSTREAM,
-						"Decompression failed for %s", display(j->in[fi]));
-				else if (ck[i] == 2u)
-					log_msg(LOG_ERROR, "%s: checksum mismatch in the frame at byte %lu",
-						display(j->in[fi]), (unsigned long)pos);
-				else
-					bad = 0;
-				if (bad) {
-					free(st);
-					free(x);
-					goto out;
-				}
-				for (k = 0; k < n; k++) {
-					out[o + 2u * k] = (uint8_t)(xi[k] >> 8);
-					out[o + 2u * k + 1u] = (uint8_t)xi[k];
-				}
-				o += 2u * (size_t)n;
-				pos += be24(raw + pos + 2);
-			}
-			free(st);
-			free(x);
+			if ((h[15] >> 4) == CMP_PREPROCESS_MODEL &&
+			    (code == CMP_ERR_PARAMS_INVALID || code == CMP_ERR_SRC_SIZE_MISMATCH))
+				log_msg(LOG_ERROR, "%s: MODEL frame without a preceding frame of its size",
+					display(j->in[fi]));
+			else if (cmp_is_error(st[f]) || st[f] != be24(h + 5) / 2u)
+				log_cmp(cmp_is_error(st[f]) ? st[f] : (uint32_t) - (int32_t)CMP_ERR_INT_BITSTREAM,
+					"Decompression failed for %s", display(j->in[fi]));
+			else if (ck[f] == 2u)
+				log_msg(LOG_ERROR, "%s: checksum mismatch in the frame at byte %lu",
+					display(j->in[fi]), (unsigned long)offs[f]);
+			else
+				continue;
+			goto out;
 		}
 	}
 	{
@@ -761,10 +695,8 @@ static int decompress_file(struct job *j, struct dev *d, int fi)
 gpu_fail:
 	log_msg(LOG_ERROR, "GPU copy failed");
 out:
-	if (d_model)
-		hipFree(d_model);
-	if (d_model_n)
-		hipFree(d_model_n);
+	free(st);
+	free(offs);
 	free(out);
 	if (owned)
 		free(raw);

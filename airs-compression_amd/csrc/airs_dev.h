@@ -214,9 +214,10 @@ uint32_t airs_dev_synth(struct airs_dev_engine *e, void *dst, uint32_t sample_by
 			uint32_t W);
 
 /* engine-owned scratch, grown on demand (stream ordered) */
-#define AIRS_NSLOT 19 /* scratch slots per engine; the last five are the device layer's (checksum
+#define AIRS_NSLOT 22 /* scratch slots per engine; the last five are the device layer's (checksum
 		       * placement, checksum products, decoder parse arrays, decoder frame info, IWT heads) */
 #define AIRS_SLOT_GATHER 11 /* slots 11..13: cmp_gpu_gather (cmp_gather.c); 0..10 cmp_host.c */
+#define AIRS_SLOT_IMAGE 14 /* slots 14..16: airs_dev_decode_image (tables, staging rows, model) */
 void *airs_dev_scratch(struct airs_dev_engine *e, int slot, size_t bytes);
 /* engine-owned device words for the gather's status exchanges (cmp_gather.c),
  * allocated with the engine so that taking part in an exchange never needs an
@@ -287,6 +288,33 @@ struct airs_decode_seq {
 	uint32_t model_in;
 };
 uint32_t airs_dev_decode_seq(struct airs_dev_engine *e, const struct airs_decode_seq *q);
+
+/* file images (cmp_gpu_decompress_image, see cmp_gpu.h; decode_image.hip): the
+ * frames at src + offsets[f], any alignment, as ONE context.  A header gather
+ * and one read-back give the sizes; the host cuts the table into chunks
+ * (cmp_image_plan.h) of at most chunk_bytes of staging; per chunk an unpack
+ * kernel writes the frames into aligned rows, airs_dev_decode_seq decodes
+ * them and an emit kernel packs the samples at dst + dst_offsets[f].  The
+ * arguments are validated by the caller (cmp_decode_image.c); what needs the
+ * headers is refused here, before anything is written: CMP_ERR_DST_TOO_SMALL,
+ * and CMP_ERR_GENERIC for a frame larger than model_samples. */
+struct airs_decode_image {
+	const void *src;
+	uint64_t src_size;
+	const uint64_t *offsets;  /* host */
+	uint32_t num_frames;
+	void *dst;
+	uint64_t dst_capacity;
+	uint64_t *dst_offsets;    /* host [num_frames + 1] */
+	uint32_t *status;
+	uint8_t *checksum_ok;
+	uint16_t *model;
+	uint32_t model_samples;
+	uint32_t *model_n;
+	uint32_t is_unsigned, model_in, big_endian;
+	uint64_t chunk_bytes;
+};
+uint32_t airs_dev_decode_image(struct airs_dev_engine *e, const struct airs_decode_image *q);
 
 /* payload-only stream (cmp_gpu_decode_stream, see cmp_gpu.h): the frame
  * pipeline over one "frame" described by the arguments instead of a header

@@ -1,6 +1,6 @@
 /* cmp_engine.h -- the opaque cmp_gpu_engine of include/cmp_gpu.h (private to
  * the library's host code: cmp_host.c, cmp_gather.c, cmp_decode_seq.c,
- * cmp_decode_stream.c) */
+ * cmp_decode_stream.c, cmp_decode_image.c) */
 #ifndef CMP_ENGINE_H
 #define CMP_ENGINE_H
 
@@ -8,6 +8,7 @@
 
 struct cmp_gpu_engine {
 	struct airs_dev_engine *dev;
+	uint32_t image_chunk; /* CMP_GPU_OPT_IMAGE_CHUNK (cmp_decode_image.c); 0: the default */
 };
 
 /* The encoder's own parameter checks (reference encoder.c:185-224), cmp_host.c:

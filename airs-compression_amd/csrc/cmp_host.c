@@ -625,6 +625,10 @@ uint32_t cmp_gpu_engine_set_option(struct cmp_gpu_engine *engine, uint32_t optio
 {
 	if (!engine)
 		return ERRV(GENERIC);
+	if (option == CMP_GPU_OPT_IMAGE_CHUNK) { /* a host-side plan: the device layer never sees it */
+		engine->image_chunk = value;
+		return 0;
+	}
 	return airs_dev_set_option(engine->dev, option, value);
 }
 

@@ -99,7 +99,10 @@ void cmp_gpu_engine_destroy(struct cmp_gpu_engine *engine);
  *                               4096 samples per segment.
  *   CMP_GPU_OPT_NO_CONTEXT_WALK 1: MODEL batches take the segment walk where
  *                               they would take the context walk (not those
- *                               with the uncompressed fallback, which need it). */
+ *                               with the uncompressed fallback, which need it).
+ *   CMP_GPU_OPT_IMAGE_CHUNK     (4, defined with cmp_gpu_decompress_image) bytes
+ *                               of engine scratch a chunk of that call may
+ *                               stage; 0: the default, 256 MiB. */
 #define CMP_GPU_OPT_EXCLUSIVE 1u
 #define CMP_GPU_OPT_WALK_SEGMENT 2u
 #define CMP_GPU_OPT_NO_CONTEXT_WALK 3u
@@ -214,6 +217,85 @@ struct cmp_gpu_decode_seq_batch {
 };
 
 uint32_t cmp_gpu_decompress_sequences(struct cmp_gpu_engine *engine, const struct cmp_gpu_decode_seq_batch *batch);
+
+/*
+ * File images: frames as they are stored -- back to back at byte granularity
+ * (the sample files' .air form, any concatenation of frame files), or at the
+ * 8-byte aligned offsets of cmp_gpu_pack_frames / cmp_gpu_gather -- decoded in
+ * one call from ONE device buffer and a table of byte offsets, into samples
+ * packed back to back, optionally big-endian as the sample files hold them.
+ *
+ * The frames form one context, in table order: frame f decodes exactly as
+ * frame (0, f) of a one-context cmp_gpu_decompress_sequences call over the
+ * same frames, with the same statuses, checksum_ok, final model and model_n
+ * (MODEL and other frames mix; a frame that fails leaves the context without
+ * a model).  A frame's slice is unusable when offsets[f] + 16 > src_size, its
+ * compressed size (header bytes 2..4) is below 16, offsets[f] + compressed
+ * size > src_size, or its original size (bytes 5..7) is odd: that frame gets
+ * CMP_ERR_INT_HDR.
+ *
+ * dst_offsets[0] = 0 and dst_offsets[f + 1] = dst_offsets[f] + the frame's
+ * header original size (0 for an unusable slice; the header's value for every
+ * other frame, whether or not it decodes), so the layout follows from the
+ * headers alone.  Frame f's samples are 16-bit (the low halves, as elsewhere),
+ * native-endian, or byte-swapped with CMP_GPU_IMG_BIG_ENDIAN; after an error
+ * the frame's own bytes are unspecified.  Nothing is written outside
+ * [dst, dst + dst_offsets[num_frames]) or outside a frame's own range.
+ *
+ * Returns CMP_ERR_NO_ERROR or a call-level refusal, raised before any sample
+ * is written: NULL engine, batch, offsets, dst_offsets or status, or
+ * num_frames 0: CMP_ERR_GENERIC; NULL src CMP_ERR_SRC_NULL; src_size 0
+ * CMP_ERR_SRC_SIZE_WRONG; NULL dst CMP_ERR_DST_NULL; odd dst
+ * CMP_ERR_DST_UNALIGNED; an unknown type or flag, model without model_n (or
+ * an odd model, model_samples 0, a status or model_n that is not 4-byte
+ * aligned), MODEL_IN without model:
+ * CMP_ERR_GENERIC; then, known after the header read-back,
+ * dst_offsets[num_frames] > dst_capacity: CMP_ERR_DST_TOO_SMALL, and a frame
+ * with more samples than model_samples while model is given: CMP_ERR_GENERIC.
+ *
+ * No byte outside the 16-byte aligned hull of [src, src + src_size) is read,
+ * and no result depends on a byte outside the frames' own slices.  The call
+ * synchronises once for the header read-back and then wherever the sequence
+ * decoder does; the device outputs are valid after cmp_gpu_synchronize.  The
+ * table is cut into chunks of at most 65535 frames whose staging rows fit
+ * CMP_GPU_OPT_IMAGE_CHUNK bytes of engine scratch (0: 256 MiB; a chunk always
+ * holds one frame at least); the model passes from chunk to chunk on the
+ * device and the result does not depend on the value.  With MODEL_IN, a
+ * model_n above the samples of the largest frame in the first chunk is not a
+ * model of these frames and counts as none.  Build-defined extension.
+ */
+#define CMP_GPU_IMG_MODEL_IN   0x1u /* the context starts from batch->model / model_n */
+#define CMP_GPU_IMG_BIG_ENDIAN 0x2u /* samples are written big-endian (the sample file format) */
+#define CMP_GPU_OPT_IMAGE_CHUNK 4u  /* cmp_gpu_engine_set_option: bytes of staging per chunk */
+
+struct cmp_gpu_decode_image {
+	enum cmp_gpu_sample_type type; /* model update extension, as cmp_gpu_decode_seq_batch */
+	const void *src;          /* device, ANY alignment */
+	uint64_t src_size;        /* bytes of the image */
+	const uint64_t *offsets;  /* HOST [num_frames]: byte offset of each frame in src, any alignment,
+				   * any order, gaps allowed; read during the call only */
+	uint32_t num_frames;      /* >= 1; no 65535 limit (the call chunks) */
+	void *dst;                /* device, 2-byte aligned; frame f's samples at dst + dst_offsets[f] */
+	uint64_t dst_capacity;    /* bytes */
+	uint64_t *dst_offsets;    /* HOST [num_frames + 1], out: valid when the call returns */
+	uint32_t *status;         /* device [num_frames]: samples decoded, or an error value */
+	uint8_t *checksum_ok;     /* device [num_frames] or NULL, as cmp_gpu_decode_seq_batch */
+	uint16_t *model;          /* device or NULL: the ONE context's model, model_samples samples */
+	uint32_t model_samples;   /* capacity of model */
+	uint32_t *model_n;        /* device, required with model: in with MODEL_IN, always out */
+	uint32_t flags;
+};
+uint32_t cmp_gpu_decompress_image(struct cmp_gpu_engine *engine, const struct cmp_gpu_decode_image *batch);
+
+/* Host only, no device: walk a HOST image of back-to-back frames from byte 0
+ * (compressed size at header bytes 2..4) and write the offsets.  Returns the
+ * number of frames found; *bad_at (optional) = the byte where the walk stopped
+ * short of `size` (a frame shorter than 16 bytes, one that runs past the end,
+ * fewer than 16 bytes left), or UINT64_MAX when the image ends exactly at a
+ * frame's end.  offsets may be NULL (count only); at most max_frames are
+ * written. */
+uint64_t cmp_gpu_frame_table(const void *image, uint64_t size, uint64_t *offsets, uint64_t max_frames,
+			     uint64_t *bad_at);
 
 /*
  * Payload-only stream: the num_samples samples at src (device) encoded as ONE
