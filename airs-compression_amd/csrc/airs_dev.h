@@ -222,8 +222,14 @@ void *airs_dev_scratch(struct airs_dev_engine *e, int slot, size_t bytes);
 /* engine-owned device words for the gather's status exchanges (cmp_gather.c),
  * allocated with the engine so that taking part in an exchange never needs an
  * allocation that could fail on one rank only: 2 words in, then
- * 2 * AIRS_COLL_MAX_RANKS words out */
+ * 2 * AIRS_COLL_MAX_RANKS words out, then the poison record: two words,
+ * {CMP_ERR_GENERIC, 0}, written when the engine is created (or the creation
+ * fails) and never again.  A rank contributes it when the upload of its own
+ * record failed, so that no peer reads what an earlier exchange left in the
+ * first two words. */
 #define AIRS_COLL_MAX_RANKS 256
+#define AIRS_COLL_POISON (2 + 2 * AIRS_COLL_MAX_RANKS) /* word offset of the poison record */
+#define AIRS_COLL_WORDS (AIRS_COLL_POISON + 2)
 uint64_t *airs_dev_coll(struct airs_dev_engine *e);
 /* engine-owned page-locked host scratch, grown on demand: asynchronous
  * read-backs and uploads; the host may rewrite it once the stream has passed
@@ -244,12 +250,17 @@ uint32_t airs_dev_patch_ids(struct airs_dev_engine *e, void *dst, uint64_t dst_s
  * AIRS_HCO_MAX_IDS frames, ids[f] for frame f).  wait polls for the signal
  * and copies the flags out (a fault count is returned as an error).
  * release MUST follow every successful begin (with ids, or NULL: no patch),
- * before any other wait on the stream; it returns 1 when the kernel patches
- * the identifiers, 0 when the caller must: NULL, more than the block holds, or
- * a second release of the same seq (wait released it on its time-out).  The
- * kernel acknowledges whether it patched; the engine checks that at the next
- * stream wait (airs_dev_sync) or commit, and patches the headers itself when
- * the kernel gave up waiting for the release. */
+ * before any other wait on the stream and before anything else is queued on
+ * it; it returns 1 when the identifiers are patched on the stream, 0 when the
+ * caller must: NULL, more than the block holds, or a second release of the
+ * same seq (wait released it on its time-out).  The kernel acknowledges
+ * whether it patched; a release with ids queues a second small kernel right
+ * behind it, which reads the acknowledgement on the device and patches the
+ * headers when the first gave up waiting for the release.  So in stream order
+ * the headers of the batch are whole after the release's kernel, from the
+ * batch's own dst, status and ids: work the caller queues after the batch
+ * (a copy of dst, the next batch into the same dst) sees them, and nothing of
+ * the commit is left for a later wait, commit or the engine's destroy. */
 #define AIRS_COMMIT_MAX_CTX 8192u /* contexts a commit kernel flags (AIRS_HCO_MAX_CTX) */
 uint32_t airs_dev_commit_begin(struct airs_dev_engine *e, const uint32_t *status, uint32_t num_ctx, uint32_t fpc,
 			       void *dst, uint64_t dst_stride, uint32_t *seq);

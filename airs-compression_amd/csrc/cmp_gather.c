@@ -195,20 +195,26 @@ static void rccl_load(void)
  * the engine: taking part never needs an allocation), and every rank gets the
  * same answer: the first non-zero status in rank order, or 0.  values[r] is
  * rank r's value.  A rank that failed locally still takes part, so its peers
- * learn of the failure instead of waiting for it in a later collective.
+ * learn of the failure instead of waiting for it in a later collective; when
+ * the upload of its record fails, it contributes the engine's poison record
+ * ({CMP_ERR_GENERIC, 0}, written once when the engine was created) instead of
+ * the words an earlier exchange left behind, which may say status 0.
  */
 static uint32_t status_exchange(struct airs_dev_engine *dev, ncclComm_t comm, hipStream_t st, int world,
 				uint32_t status, uint64_t value, uint64_t *values)
 {
 	uint64_t rec[2] = {status, value}, all[2 * AIRS_COLL_MAX_RANKS];
 	uint64_t *d = airs_dev_coll(dev);
+	const uint64_t *mine = d;
 	uint32_t e = 0, first = 0;
 	int r;
 
 	/* an upload that fails still leaves the rank in the all-gather */
-	if (airs_dev_h2d(dev, d, rec, sizeof(rec)))
+	if (airs_dev_h2d(dev, d, rec, sizeof(rec))) {
 		first = ERRV(GENERIC);
-	NCCL_OK(R.all_gather(d, d + 2, sizeof(rec), ncclUint8, comm, st));
+		mine = d + AIRS_COLL_POISON;
+	}
+	NCCL_OK(R.all_gather(mine, d + 2, sizeof(rec), ncclUint8, comm, st));
 	e = airs_dev_d2h(dev, all, d + 2, (size_t)world * sizeof(rec));
 	if (!e)
 		e = airs_dev_sync(dev);
@@ -233,6 +239,21 @@ out:
  * call.  Only an engine or communicator of NULL, a world over
  * AIRS_COLL_MAX_RANKS, or a missing RCCL returns at once: such a rank cannot
  * take part at all.
+ *
+ * What is NOT collective: a device or RCCL call that fails on one rank after
+ * an exchange it has passed.  These stay local to that rank, which returns
+ * CMP_ERR_GENERIC (or the call's error) while its peers may return another
+ * value or wait in the next collective for it:
+ *   - the upload of the size table (after exchange 1): the rank leaves before
+ *     the table's all-gather;
+ *   - the read-back and the stream wait after an all-gather (a status
+ *     exchange's, or the size table's): the rank's peers have their answer,
+ *     this rank does not;
+ *   - the RCCL calls themselves (an all-gather, the group's start, send, recv
+ *     and end);
+ *   - a non-root's final stream wait, after its send, and the root's
+ *     identifier uploads, patch and final wait, after its receives.
+ * The failed upload of a status record is collective: see status_exchange.
  */
 uint32_t cmp_gpu_gather(struct cmp_gpu_engine *engine, void *nccl_comm, uint32_t root, uint32_t layout, uint32_t fpc,
 			const void *frames, uint64_t frame_stride, uint32_t frame_capacity, const uint32_t *sizes,

@@ -1021,10 +1021,9 @@ __global__ void patch_ids_kernel(uint8_t *dst, uint64_t stride, uint32_t num, ui
 // waits for the host's release (bounded: `ticks` of the 100 MHz clock, ~1 s)
 // and, if the release says so, writes the identifiers the host put in the
 // block into the headers of the frames without an error (as
-// patch_ids_kernel).  Last, its acknowledgement: whether it patched, so that
-// a host whose release came after the kernel gave up patches the headers
-// itself.  The stream's next work waits behind it, and no host
-// launch is needed.
+// patch_ids_kernel).  Last, its acknowledgement: whether it patched, for
+// commit_repair_kernel, which the release queues right behind it (ADVICE r5,
+// r6).  The stream's next work waits behind the two.
 __global__ void commit_kernel(const uint32_t *status, uint32_t num_ctx, uint32_t fpc, const uint32_t *ticket,
 			      volatile uint32_t *hco, uint32_t seq, uint8_t *dst, uint64_t dst_stride, uint64_t ticks)
 {
@@ -1077,6 +1076,27 @@ __global__ void commit_kernel(const uint32_t *status, uint32_t num_ctx, uint32_t
 	if (threadIdx.x == 0) {
 		__threadfence_system();
 		hco[AIRS_HCO_ACK] = ((seq & 0x7FFFFFFFu) << 1) | 1u;
+	}
+}
+
+// The repair of a commit kernel that gave up before its release came: queued
+// by the release, so it runs right behind commit kernel `seq`, ahead of
+// whatever the caller queues after the batch.  It reads that kernel's
+// acknowledgement on the device and, unless it says "patched", writes the
+// release's identifiers (`ids`: the engine's page-locked copy, read over the
+// bus) as patch_ids_kernel does, with the batch's own dst and statuses.
+__global__ void commit_repair_kernel(const volatile uint32_t *hco, uint32_t seq, uint8_t *dst, uint64_t dst_stride,
+				     uint32_t total, const uint64_t *ids, const uint32_t *status)
+{
+	if (hco[AIRS_HCO_ACK] == (((seq & 0x7FFFFFFFu) << 1) | 1u))
+		return;
+	for (uint32_t f = threadIdx.x; f < total; f += blockDim.x) { // one workgroup, as commit_kernel
+		if (status[f] > ERRV(128u))
+			continue;
+		uint8_t *p = dst + (uint64_t)f * dst_stride + 8u;
+		const uint64_t id = ids[f];
+		for (int b = 0; b < 6; b++)
+			p[b] = (uint8_t)(id >> (40 - 8 * b));
 	}
 }
 
@@ -1196,21 +1216,19 @@ struct airs_dev_engine {
 	volatile uint32_t *hco; // coherent page-locked block (AIRS_HCO_*), written in-stream
 	uint32_t hco_seq;       // the last sequence word asked for
 	uint32_t hco_released;  // the last sequence word released (airs_dev_commit_release)
-	uint64_t commit_ticks;  // the commit kernel's wait for the release (100 MHz ticks)
+	// the commit kernel's wait for the release (100 MHz ticks): entry i mod
+	// commit_ticks_n for the i-th airs_dev_commit_begin (one entry unless
+	// AIRS_TEST_COMMIT_TICKS lists several)
+	uint64_t commit_ticks[8];
+	uint32_t commit_ticks_n, commit_begun;
 	uint64_t commit_polls;  // the host's wait for the commit kernel's signal (pause loops)
-	// a release with identifiers whose patch is not yet confirmed by the
-	// kernel's acknowledgement (checked at the next stream wait): its seq (0:
-	// none), the frames and the identifiers (page-locked: patch_ids_kernel
+	// the commit kernel last begun: what its release hands to
+	// commit_repair_kernel, with the identifiers (page-locked: the repair
 	// reads them over the bus if the kernel gave up)
-	uint32_t commit_total;   // the frames of the commit kernel last begun
 	void *commit_dst;
 	uint64_t commit_dst_stride;
 	const uint32_t *commit_status;
-	uint32_t pend_seq, pend_total, pend_buf; // the pending release (pend_seq 0: none)
-	void *pend_dst;
-	uint64_t pend_dst_stride;
-	const uint32_t *pend_status;
-	uint64_t *commit_ids[2]; // two buffers: a patch queued for release N reads its own
+	uint64_t *commit_ids[2]; // two buffers: repair N reads commit_ids[N & 1] (airs_dev_commit_release)
 	size_t commit_ids_cap[2];
 	// cmp_gpu_engine_set_option (include/cmp_gpu.h)
 	uint32_t opt_exclusive;     // CMP_GPU_OPT_EXCLUSIVE
@@ -1252,8 +1270,6 @@ extern "C" const char *airs_dev_last_error(void)
 	return g_err;
 }
 
-static int commit_verify(struct airs_dev_engine *e);
-
 extern "C" struct airs_dev_engine *airs_dev_engine_create(void *stream)
 {
 	if (!airs_dev_available()) {
@@ -1265,8 +1281,15 @@ extern "C" struct airs_dev_engine *airs_dev_engine_create(void *stream)
 		return nullptr;
 	e->stream = (hipStream_t)stream;
 	// 256 bytes of tickets and fault words, then the gather's status words
-	const size_t tbytes = 256u + 16u * (AIRS_COLL_MAX_RANKS + 1u);
-	if (hipMalloc(&e->ticket, tbytes) != hipSuccess || hipMemset(e->ticket, 0, tbytes) != hipSuccess) {
+	// and, written here once and never again, its poison record
+	const size_t tbytes = 256u + 8u * AIRS_COLL_WORDS;
+	const uint64_t poison[2] = {ERRV(E_GENERIC), 0u};
+	if (hipMalloc(&e->ticket, tbytes) != hipSuccess)
+		e->ticket = nullptr;
+	if (!e->ticket || hipMemset(e->ticket, 0, tbytes) != hipSuccess ||
+	    hipMemcpy((uint8_t *)e->ticket + tbytes - sizeof(poison), poison, sizeof(poison), hipMemcpyHostToDevice) !=
+		    hipSuccess) {
+		(void)hipFree(e->ticket);
 		free(e);
 		return nullptr;
 	}
@@ -1278,11 +1301,21 @@ extern "C" struct airs_dev_engine *airs_dev_engine_create(void *stream)
 	}
 	e->hco = (volatile uint32_t *)hf;
 	// the commit handshake's bounds; AIRS_TEST_COMMIT_TICKS / _POLLS shorten
-	// them to force its give-up paths (tests only)
-	e->commit_ticks = 100000000ull;
+	// them to force its give-up paths (tests only).  _TICKS takes one value
+	// or a comma-separated list, one entry per commit in turn, so that a test
+	// can make some commit kernels give up and others not.
+	e->commit_ticks[0] = 100000000ull;
+	e->commit_ticks_n = 1u;
 	e->commit_polls = 1ull << 26;
-	if (const char *t = getenv("AIRS_TEST_COMMIT_TICKS"))
-		e->commit_ticks = strtoull(t, nullptr, 10);
+	if (const char *t = getenv("AIRS_TEST_COMMIT_TICKS")) {
+		uint32_t k = 0;
+		char *end;
+		do {
+			e->commit_ticks[k++] = strtoull(t, &end, 10);
+			t = end + 1;
+		} while (*end == ',' && k < 8u);
+		e->commit_ticks_n = k;
+	}
 	if (const char *t = getenv("AIRS_TEST_COMMIT_POLLS"))
 		e->commit_polls = strtoull(t, nullptr, 10);
 	e->hco[AIRS_HCO_FAULT] = 0u;
@@ -1298,8 +1331,6 @@ extern "C" void airs_dev_engine_destroy(struct airs_dev_engine *e)
 	if (!e)
 		return;
 	(void)hipStreamSynchronize(e->stream);
-	if (commit_verify(e))
-		(void)hipStreamSynchronize(e->stream);
 	(void)hipFree(e->agg);
 	(void)hipFree(e->tail);
 	(void)hipFree(e->ticket);
@@ -2290,9 +2321,8 @@ extern "C" uint32_t airs_dev_commit_begin(struct airs_dev_engine *e, const uint3
 	e->commit_dst = dst;
 	e->commit_dst_stride = dst_stride;
 	e->commit_status = status;
-	e->commit_total = num_ctx * fpc;
 	hipLaunchKernelGGL(commit_kernel, dim3(1), dim3(256), 0, e->stream, status, num_ctx, fpc, e->ticket, e->hco, *seq,
-			   (uint8_t *)dst, dst_stride, e->commit_ticks);
+			   (uint8_t *)dst, dst_stride, e->commit_ticks[e->commit_begun++ % e->commit_ticks_n]);
 	HIPCHECK(hipGetLastError());
 	return 0;
 }
@@ -2305,8 +2335,6 @@ extern "C" uint32_t airs_dev_commit_wait(struct airs_dev_engine *e, uint32_t seq
 {
 	for (uint64_t i = 0; i < e->commit_polls; i++) { // ~ a second of polls
 		if (e->hco[AIRS_HCO_SEQ] == seq) {
-			// the previous commit kernel ran before this one: its acknowledgement is final
-			commit_verify(e);
 			const uint32_t faults = e->hco[AIRS_HCO_FAULT];
 			memcpy(flags, (const void *)((const volatile uint8_t *)e->hco + AIRS_HCO_FLAGS), num_ctx);
 			if (faults) {
@@ -2330,12 +2358,24 @@ extern "C" uint32_t airs_dev_commit_wait(struct airs_dev_engine *e, uint32_t seq
 	return 0;
 }
 
-// Release the commit kernel of `seq`: 1 when it patches the identifiers
-// (ids given: the engine checks the kernel's acknowledgement at the next
-// stream wait or commit, and patches the headers itself if the kernel gave
-// up waiting for this release), 0 when the caller must patch them
-// (no ids, more than the block holds, or a second release of the same seq:
-// commit_wait released it on its time-out, with mode 0).
+// Release the commit kernel of `seq`: 1 when the identifiers are patched on
+// the stream behind it, 0 when the caller must patch them (no ids, more than
+// the block holds, or a second release of the same seq: commit_wait released
+// it on its time-out, with mode 0).  With ids, commit_repair_kernel is queued
+// here.  Nothing is on the stream behind commit kernel `seq` yet, so the
+// headers are whole before anything the caller queues after the batch, even
+// when the kernel gave up waiting for this release; the
+// repair has the batch's own dst, statuses and identifiers as arguments, and
+// nothing is left for a later stream wait, commit or the engine's destroy.
+//
+// commit_ids[seq & 1] is the repair's copy of the identifiers.  A release
+// with ids follows its own commit kernel's signal (commit_wait saw it; after
+// its time-out the release is the second of its seq and returns above), and
+// that kernel runs behind repair seq - 1 on the stream, which is behind
+// repair seq - 2.  So when this release writes the buffer, or frees it to
+// grow it, the repair that last read it (seq - 2) has ended, and repair
+// seq - 1 reads the other buffer.  The same order lets this release rewrite
+// the block's identifiers, which commit kernel seq - 1 may have read.
 extern "C" int airs_dev_commit_release(struct airs_dev_engine *e, uint32_t seq, const uint64_t *ids, uint32_t total)
 {
 	if (e->hco_released == seq)
@@ -2357,44 +2397,22 @@ extern "C" int airs_dev_commit_release(struct airs_dev_engine *e, uint32_t seq, 
 	if (ids) {
 		memcpy((void *)((volatile uint8_t *)e->hco + AIRS_HCO_IDS), ids, (size_t)total * 8u);
 		memcpy(e->commit_ids[b], ids, (size_t)total * 8u);
-		e->pend_seq = seq;
-		e->pend_total = total;
-		e->pend_buf = b;
-		e->pend_dst = e->commit_dst;
-		e->pend_dst_stride = e->commit_dst_stride;
-		e->pend_status = e->commit_status;
 	}
 	e->hco[AIRS_HCO_MODE] = ids ? 1u : 0u;
 	__atomic_thread_fence(__ATOMIC_SEQ_CST);
 	e->hco[AIRS_HCO_GO] = seq;
-	return ids ? 1 : 0;
-}
-
-// The pending release's acknowledgement, once its commit kernel has ended
-// (after a stream wait, or once the next commit kernel has signalled): a
-// kernel that gave up before the release came left the headers alone, so
-// the identifiers are patched here (queued on the stream; sync_wait waits
-// for it).  Returns 1 when a patch was queued.
-static int commit_verify(struct airs_dev_engine *e)
-{
-	if (!e->pend_seq)
+	if (!ids)
 		return 0;
-	const uint32_t seq = e->pend_seq, ack = e->hco[AIRS_HCO_ACK];
-	e->pend_seq = 0u;
-	if ((ack & ~1u) == ((seq & 0x7FFFFFFFu) << 1) && (ack & 1u))
-		return 0;
-	// (the next write of this buffer is release seq + 2, after this patch ran)
-	hipLaunchKernelGGL(patch_ids_kernel, dim3((e->pend_total + 255u) / 256u), dim3(256), 0, e->stream,
-			   (uint8_t *)e->pend_dst, e->pend_dst_stride, e->pend_total, 0u, 1u,
-			   (const uint64_t *)e->commit_ids[e->pend_buf], e->pend_status);
+	// after the release, so that the waiting kernel does not wait for this launch too
+	hipLaunchKernelGGL(commit_repair_kernel, dim3(1), dim3(256), 0, e->stream, e->hco, seq, (uint8_t *)e->commit_dst,
+			   e->commit_dst_stride, total, (const uint64_t *)e->commit_ids[b], e->commit_status);
+	// (not queued: the caller patches; the kernel may have written the same identifiers)
 	return hipGetLastError() == hipSuccess ? 1 : 0;
 }
 
 static uint32_t sync_wait(struct airs_dev_engine *e, bool waited)
 {
 	if (!waited)
-		HIPCHECK(hipStreamSynchronize(e->stream));
-	if (commit_verify(e)) // a commit kernel gave up: the headers patched from here
 		HIPCHECK(hipStreamSynchronize(e->stream));
 	const uint32_t faults = e->hco[AIRS_HCO_FAULT];
 #if AIRS_ABLATE

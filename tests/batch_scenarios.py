@@ -146,3 +146,74 @@ def run_batch_gpu(lib, eng, api, params, kind, n, nctx, fpc, cap, srcs, ts_start
         return tuple(frames), tuple(state)
     finally:
         lib.set_timestamp_func(None)
+
+
+def call_frames(frames, nctx, fpc, a0, k):
+    """Rows of the call over acquisitions a0 .. a0+k-1, from frames in
+    (context, acquisition) order: row c*k + (a-a0) is frame c*fpc + a."""
+    return tuple(frames[c * fpc + a] for c in range(nctx) for a in range(a0, a0 + k))
+
+
+def run_batch_gpu_reused(lib, eng, api, params, kind, n, nctx, fpc, cap, srcs, splits, ts_start=5000, flags=0,
+                         close_before_wait=False):
+    """The calls of `splits` on the same contexts, every call writing to the
+    SAME dst and sizes tensors at offset 0 (src advances as in run_batch_gpu),
+    as a caller may who relies on cmp_gpu_compress being asynchronous on the
+    engine's stream.  `eng` must be bound to torch's current stream: after
+    each call dst.clone() and sizes.clone() are queued on it, and nothing
+    waits on the host between the calls; the first host wait comes after the
+    last snapshot.  close_before_wait: the engine is destroyed (eng.close())
+    before that first wait; every tensor stays alive past it.
+
+    Returns (snapshots, final, state): snapshots[j] the rows of call j as read
+    from its clones, final the rows read from dst and sizes after the wait
+    (the last call's), each row (size, bytes or None); state as
+    run_batch_gpu's."""
+    import torch
+    sb = 4 if kind == "i16_in_i32" else 2
+    pcs = _per_ctx(params, nctx)
+    stride = n * sb
+    calls = _calls(fpc, splits)
+    kmax = max(k for _, k in calls)
+    order = [c * fpc + a for a0, k in calls for c in range(nctx) for a in range(a0, a0 + k)]
+    host_src = np.concatenate([np.ascontiguousarray(srcs[f]).view(np.uint8) for f in order])
+    src = torch.from_numpy(host_src).cuda()
+    dstride = (cap + 64 + 7) // 8 * 8
+    dst = torch.full((nctx * kmax * dstride,), 0xAB, dtype=torch.uint8, device="cuda")
+    sizes = torch.zeros(nctx * kmax, dtype=torch.int32, device="cuda")
+    lib.set_timestamp_func(_ts_counter(ts_start))
+    try:
+        wbs = max(_work_size(lib, api, p, stride) for p in pcs)
+        wstride = (max(wbs, 2) + 15) // 16 * 16
+        work = torch.zeros(nctx * wstride, dtype=torch.uint8, device="cuda")
+        ctxs = (api.CmpContext * nctx)()
+        for c in range(nctx):
+            w = _work_size(lib, api, pcs[c], stride)
+            r = lib.initialise(ctxs[c], pcs[c], work.data_ptr() + c * wstride if w else None, w)
+            assert not api.is_error(r), api.error_name(r)
+        torch.cuda.synchronize()
+        clones, off = [], 0
+        for a0, k in calls:  # no host wait in this loop
+            r = eng.compress(ctxs, k, kind, src.data_ptr() + off * stride, stride, stride, dst.data_ptr(), dstride,
+                             cap, sizes.data_ptr(), flags)
+            assert r == 0, api.error_name(r)
+            clones.append((dst.clone(), sizes.clone()))
+            off += nctx * k
+        if close_before_wait:
+            eng.close()
+        torch.cuda.synchronize()
+
+        def rows(d, s, k):
+            sz = s.cpu().numpy().astype(np.uint32)
+            host = d.cpu().numpy()
+            return tuple((int(sz[j]), bytes(host[j * dstride:j * dstride + int(sz[j])])
+                          if not api.is_error(int(sz[j])) else None) for j in range(nctx * k))
+
+        snapshots = [rows(d, s, k) for (d, s), (_, k) in zip(clones, calls)]
+        final = rows(dst, sizes, calls[-1][1])
+        wk = work.cpu().numpy()
+        state = [(ctxs[c].identifier, ctxs[c].sequence_number, ctxs[c].model_size,
+                  bytes(wk[c * wstride:c * wstride + wbs])) for c in range(nctx)]
+        return snapshots, final, tuple(state)
+    finally:
+        lib.set_timestamp_func(None)

@@ -28,12 +28,15 @@ struct airs_dev_engine {
 	void *pinned;
 	size_t pinned_cap;
 	uint64_t salt;
-	uint64_t coll[2 + 2 * AIRS_COLL_MAX_RANKS];
+	uint64_t coll[AIRS_COLL_WORDS]; /* the last two: the poison record */
 };
 
 /* failure injection for the multi-rank gather harness (gather_sim.c): the
  * scratch slot whose allocation fails on this thread (-1: none) */
 __thread int stub_scratch_fail_slot = -1;
+/* ... and the airs_dev_h2d on this thread that fails and copies nothing:
+ * the k-th from now (1: the next one; 0: none) */
+__thread int stub_h2d_fail_at;
 
 uint64_t *airs_dev_coll(struct airs_dev_engine *e)
 {
@@ -60,8 +63,12 @@ const char *airs_dev_last_error(void)
 
 struct airs_dev_engine *airs_dev_engine_create(void *stream)
 {
+	struct airs_dev_engine *e = calloc(1, sizeof(struct airs_dev_engine));
+
 	(void)stream;
-	return calloc(1, sizeof(struct airs_dev_engine));
+	if (e)
+		e->coll[AIRS_COLL_POISON] = ERRV(1u); /* CMP_ERR_GENERIC, as the device layer's create */
+	return e;
 }
 
 uint32_t airs_dev_set_option(struct airs_dev_engine *e, uint32_t option, uint32_t value)
@@ -420,6 +427,8 @@ void airs_dev_free(void *p)
 uint32_t airs_dev_h2d(struct airs_dev_engine *e, void *dst, const void *src, size_t bytes)
 {
 	(void)e;
+	if (stub_h2d_fail_at && --stub_h2d_fail_at == 0)
+		return ERRV(1u);
 	memcpy(dst, src, bytes);
 	return 0;
 }

@@ -6,7 +6,8 @@
  * plain gather (the root's buffer, table and patched identifiers checked
  * against the frames), or a refusal on ONE rank (the root's capacity,
  * alignment or NULL buffer, a peer's NULL frames, an allocation failing on one
- * rank, an error-valued size, a frame that made no draw).  Every rank must
+ * rank, an error-valued size, a frame that made no draw, the upload of a
+ * status exchange failing on one rank).  Every rank must
  * return the same value and none may be left waiting: a watchdog ends a run
  * that hangs (exit 3).  Prints "rets r0 r1 ...".
  *   usage: gather_sim WORLD ROOT SCENARIO [LAYOUT]
@@ -27,11 +28,18 @@ struct ncclComm;
 struct fake_shared *fake_shared_new(int world);
 struct ncclComm *fake_comm(struct fake_shared *s, int rank);
 extern __thread int stub_scratch_fail_slot;
+extern __thread int stub_h2d_fail_at;
 
 enum {
 	S_OK, S_ROOT_SMALL, S_ROOT_MISALIGNED, S_ROOT_OUT_NULL, S_PEER_FRAMES_NULL, S_PEER_FAIL_TABLE,
-	S_PEER_FAIL_PACK, S_ROOT_FAIL_TABLE, S_ROOT_FAIL_PATCH, S_ERROR_SIZE, S_NO_DRAW, S_NSCEN
+	S_PEER_FAIL_PACK, S_ROOT_FAIL_TABLE, S_ROOT_FAIL_PATCH, S_ERROR_SIZE, S_NO_DRAW, S_PEER_FAIL_UPLOAD1,
+	S_ROOT_FAIL_UPLOAD1, S_PEER_FAIL_UPLOAD2, S_NSCEN
 };
+
+/* a rank's uploads (airs_dev_h2d) in cmp_gpu_gather, in order: the first
+ * status exchange's {status, value}, the size table, the second exchange's */
+#define H2D_EXCHANGE1 1
+#define H2D_EXCHANGE2 3
 
 #define F 6         /* frames per rank */
 #define STRIDE 512u /* frame stride and capacity */
@@ -79,6 +87,12 @@ static void *rank_main(void *arg)
 		stub_scratch_fail_slot = AIRS_SLOT_GATHER + 1;
 	if (SC == S_ROOT_FAIL_PATCH && r == ROOT)
 		stub_scratch_fail_slot = AIRS_SLOT_GATHER + 2;
+	/* (the second exchange's upload fails after a first exchange that left
+	 * status 0 in this rank's collective words) */
+	if ((SC == S_PEER_FAIL_UPLOAD1 && r == (ROOT + 1) % W) || (SC == S_ROOT_FAIL_UPLOAD1 && r == ROOT))
+		stub_h2d_fail_at = H2D_EXCHANGE1;
+	if (SC == S_PEER_FAIL_UPLOAD2 && r == (ROOT + 1) % W)
+		stub_h2d_fail_at = H2D_EXCHANGE2;
 	if (r == ROOT) {
 		int rr;
 

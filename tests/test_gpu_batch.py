@@ -305,6 +305,139 @@ def test_batch_commit_give_up_paths(prod, orc, knob):
     assert not bad, f"frames {bad[:8]} differ"
 
 
+COMMIT_TICKS_DEFAULT = "100000000"  # the commit kernel's wait without the knob (encode.hip: ~1 s of the 100 MHz clock)
+
+
+@pytest.fixture(scope="module")
+def reuse_case(orc):
+    """The give-up test's shapes (u16, 16 Ki samples, 8 contexts, strided work
+    buffers, fallback and checksums on, random walks that compress: the batch
+    takes batch_walk_spec and the commit kernel patches), but with ONE
+    secondary pass and three calls of two acquisitions, so that every call
+    starts with a primary pass that draws a new identifier.  The oracle's
+    frames once, for all the buffer-reuse tests below."""
+    import numpy as np
+    P = api.CmpParams
+    params = P(primary_preprocessing=1, primary_encoder_type=1, primary_encoder_param=16,
+               secondary_iterations=1, secondary_preprocessing=3, secondary_encoder_type=2,
+               secondary_encoder_param=8, secondary_encoder_outlier=107, model_rate=11,
+               checksum_enabled=1, uncompressed_fallback_enabled=1)
+    rng = np.random.default_rng(404)
+    n, nctx, fpc, splits = 16384, 8, 6, [2, 2, 2]
+    srcs = []
+    for c in range(nctx):
+        base = np.cumsum(rng.integers(-3, 4, n))
+        for a in range(fpc):
+            v = (base + rng.integers(-4, 5, n)).astype(np.int64)  # nothing falls back: the kernel patches
+            srcs.append((v & 0xFFFF).astype(np.uint16))
+    cap = 26 + 6 * n
+    want = bs.run_batch_host(orc, api, params, "u16", n, nctx, fpc, cap, srcs, splits=splits)
+    assert all(b is not None and api.parse_header(b)["encoder_type"] != api.ENCODER_UNCOMPRESSED for _, b in want[0])
+    calls = [bs.call_frames(want[0], nctx, fpc, a0, 2) for a0 in (0, 2, 4)]
+    # precondition (CPU only): in every context each call's identifiers (header bytes 8..13) differ from
+    # the previous call's in some row, so that identifiers left over from the previous call would show
+    for c in range(nctx):
+        ids = [[b[8:14] for _, b in rows[2 * c:2 * c + 2]] for rows in calls]
+        for j in range(1, len(calls)):
+            assert any(x != y for x, y in zip(ids[j], ids[j - 1])), (c, j)
+        assert all(x != b"\0" * 6 for call in ids for x in call), c
+    # the first call alone (test d): the same frames, and the states after two acquisitions
+    first = [srcs[c * fpc + a] for c in range(nctx) for a in range(2)]
+    want1 = bs.run_batch_host(orc, api, params, "u16", n, nctx, 2, cap, first)
+    assert want1[0] == calls[0]
+    return dict(params=params, n=n, nctx=nctx, fpc=fpc, splits=splits, srcs=srcs, cap=cap, calls=calls,
+                state=want[1], first=first, first_state=want1[1])
+
+
+def _run_reused(prod, case, env, first_only=False, close_before_wait=False):
+    """run_batch_gpu_reused on an engine created on torch's current stream
+    with the knobs of `env` set while it is created (it reads them then)."""
+    import os
+
+    import torch
+    os.environ.update(env)
+    try:
+        e = prod.engine(torch.cuda.current_stream().cuda_stream)
+    finally:
+        for k in env:
+            del os.environ[k]
+    try:
+        if first_only:
+            return bs.run_batch_gpu_reused(prod, e, api, case["params"], "u16", case["n"], case["nctx"], 2,
+                                           case["cap"], case["first"], [2], close_before_wait=close_before_wait)
+        return bs.run_batch_gpu_reused(prod, e, api, case["params"], "u16", case["n"], case["nctx"], case["fpc"],
+                                       case["cap"], case["srcs"], case["splits"])
+    finally:
+        e.close()
+
+
+def _rows_differ(got, want, prev):
+    """The rows that differ; when only the identifier differs, the one found
+    (and whether it is the previous call's for that row)."""
+    out = []
+    for j, (g, w) in enumerate(zip(got, want)):
+        if g != w:
+            if g[0] == w[0] and g[1] is not None and g[1][:8] + g[1][14:] == w[1][:8] + w[1][14:]:
+                stale = " (the previous call's)" if prev and g[1][8:14] == prev[j][1][8:14] else ""
+                out.append(f"row {j}: identifier {g[1][8:14].hex()}{stale}, want {w[1][8:14].hex()}")
+            else:
+                out.append(f"row {j}: frame differs")
+    return out
+
+
+def _check_reused(case, got, ncalls=3, state="state"):
+    """Every snapshot, the final buffers and the states, all looked at before
+    the one assertion, so that a failure shows where identifiers went wrong."""
+    snapshots, final, st = got
+    assert len(snapshots) == ncalls
+    calls, bad = case["calls"], []
+    for j, snap in enumerate(snapshots):
+        d = _rows_differ(snap, calls[j], calls[j - 1] if j else None)
+        if d:
+            bad.append(f"snapshot behind call {j}: {len(d)} rows, {d[:3]}")
+    d = _rows_differ(final, calls[ncalls - 1], calls[ncalls - 2] if ncalls > 1 else None)
+    if d:
+        bad.append(f"final dst: {len(d)} rows, {d[:3]}")
+    assert not bad, "\n".join(bad)
+    assert st == case[state], "context states or work buffers differ"
+
+
+def test_batch_reused_buffers(prod, reuse_case):
+    """cmp_gpu_compress is asynchronous on the engine's stream, so
+    a caller may copy dst behind a call and start the next batch into the same
+    dst and sizes without a host wait.  Control, no knob: the snapshot queued
+    behind every call and the final buffers equal the oracle's frames of that
+    call, identifiers unmasked; context states and work buffers too."""
+    _check_reused(reuse_case, _run_reused(prod, reuse_case, {}))
+
+
+@pytest.mark.parametrize("knob", ["AIRS_TEST_COMMIT_TICKS", "AIRS_TEST_COMMIT_POLLS"])
+def test_batch_reused_buffers_give_up(prod, reuse_case, knob):
+    """... with every commit kernel giving up its wait for the release at
+    once (TICKS=0), or the host its wait for the signal (POLLS=0): the
+    identifiers must be in the headers in stream order, in the snapshot queued
+    right behind each call, not only after a later host wait."""
+    _check_reused(reuse_case, _run_reused(prod, reuse_case, {knob: "0"}))
+
+
+@pytest.mark.parametrize("ticks", ["0," + COMMIT_TICKS_DEFAULT, COMMIT_TICKS_DEFAULT + ",0"],
+                         ids=["even_give_up", "odd_give_up"])
+def test_batch_reused_buffers_give_up_some_calls(prod, reuse_case, ticks):
+    """... with the commit kernels of the even calls giving up and the others
+    not (AIRS_TEST_COMMIT_TICKS as a list, one entry per commit in turn), and
+    the reverse: a repair of call N that ran behind call N+1 would put call
+    N's identifiers over those that commit kernel N+1 wrote into the same dst."""
+    _check_reused(reuse_case, _run_reused(prod, reuse_case, {"AIRS_TEST_COMMIT_TICKS": ticks}))
+
+
+def test_batch_commit_give_up_then_destroy(prod, reuse_case):
+    """... and one call whose commit kernel gave up, then the engine's destroy
+    with no host wait before it: the snapshot queued behind the call and dst
+    hold the identifiers (every tensor stays alive past the destroy)."""
+    got = _run_reused(prod, reuse_case, {"AIRS_TEST_COMMIT_TICKS": "0"}, first_only=True, close_before_wait=True)
+    _check_reused(reuse_case, got, ncalls=1, state="first_state")
+
+
 def test_batch_mixed_fallback_model_contexts(prod, eng, orc):
     """contexts with and without the uncompressed fallback
     in one batch (different parameters: the host-stepped path), with
