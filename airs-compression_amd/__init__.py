@@ -32,6 +32,7 @@ OPT_NO_CONTEXT_WALK = 3
 OPT_IMAGE_CHUNK = 4  # CMP_GPU_OPT_IMAGE_CHUNK: bytes of staging per chunk of decompress_image (0: 256 MiB)
 IMG_MODEL_IN = 0x1  # CMP_GPU_IMG_MODEL_IN (cmp_gpu_decompress_image)
 IMG_BIG_ENDIAN = 0x2  # CMP_GPU_IMG_BIG_ENDIAN
+IMG_SRC_BIG_ENDIAN = 0x1  # CMP_GPU_IMG_SRC_BIG_ENDIAN (cmp_gpu_compress_image)
 KIND_TO_GPU = {"u16": GPU_U16, "i16": GPU_I16, "i16_in_i32": GPU_I16_IN_I32}
 
 
@@ -137,6 +138,24 @@ class GpuDecodeImage(ctypes.Structure):
     ]
 
 
+class GpuEncodeImage(ctypes.Structure):
+    """struct cmp_gpu_encode_image (include/cmp_gpu.h)."""
+    _fields_ = [
+        ("type", c_int),
+        ("src", c_void_p),
+        ("src_size", c_uint64),
+        ("offsets", c_void_p),
+        ("frame_bytes", c_void_p),
+        ("num_frames", c_uint32),
+        ("out", c_void_p),
+        ("out_capacity", c_uint64),
+        ("out_offsets", c_void_p),
+        ("sizes", c_void_p),
+        ("batch_flags", c_uint32),
+        ("flags", c_uint32),
+    ]
+
+
 class AirsLib(CmpLib):
     """CmpLib plus the cmp_gpu.h device batch API."""
 
@@ -179,6 +198,8 @@ class AirsLib(CmpLib):
         L.cmp_gpu_gather_plan.restype = c_uint32
         L.cmp_gpu_decompress_image.argtypes = [c_void_p, POINTER(GpuDecodeImage)]
         L.cmp_gpu_decompress_image.restype = c_uint32
+        L.cmp_gpu_compress_image.argtypes = [c_void_p, POINTER(CmpContext), POINTER(GpuEncodeImage)]
+        L.cmp_gpu_compress_image.restype = c_uint32
         L.cmp_gpu_frame_table.argtypes = [c_void_p, c_uint64, c_void_p, c_uint64, POINTER(c_uint64)]
         L.cmp_gpu_frame_table.restype = c_uint64
 
@@ -302,6 +323,26 @@ class GpuEngine:
                            model_samples=model_samples, model_n=model_n_ptr or None, flags=flags)
         r = self.lib.lib.cmp_gpu_decompress_image(self.handle, ctypes.byref(b))
         return int(r), dof
+
+    def compress_image(self, ctx, kind: str, src_ptr: int, src_size: int, offsets, frame_bytes, out_ptr: int,
+                       out_capacity: int, out_offsets_ptr: int, sizes_ptr: int, batch_flags: int = 0,
+                       flags: int = 0) -> int:
+        """cmp_gpu_compress_image: the sample frames at src + offsets[f] (host
+        tables of byte offsets and sizes, any alignment, unequal sizes)
+        compressed as the ONE context ctx (a CmpContext) into a packed .air
+        image at out; out_offsets (device uint64 [num_frames + 1]) and sizes
+        (device uint32 [num_frames]) are valid after synchronize (flags:
+        IMG_SRC_BIG_ENDIAN; batch_flags: GPU_AUTO_RICE, ...)."""
+        import numpy as np
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        fb = np.ascontiguousarray(frame_bytes, dtype=np.uint32)
+        if offs.size != fb.size:
+            raise ValueError("offsets and frame_bytes differ in length")
+        b = GpuEncodeImage(type=KIND_TO_GPU[kind], src=src_ptr or None, src_size=src_size,
+                           offsets=offs.ctypes.data, frame_bytes=fb.ctypes.data, num_frames=offs.size,
+                           out=out_ptr or None, out_capacity=out_capacity, out_offsets=out_offsets_ptr or None,
+                           sizes=sizes_ptr or None, batch_flags=batch_flags, flags=flags)
+        return int(self.lib.lib.cmp_gpu_compress_image(self.handle, ctypes.byref(ctx), ctypes.byref(b)))
 
     def encode_stream(self, kind: str, src_ptr: int, num_samples: int, preprocessing: int, encoder_type: int,
                       encoder_param: int, encoder_outlier: int, dst_ptr: int, dst_capacity: int,

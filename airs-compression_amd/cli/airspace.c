@@ -11,14 +11,16 @@
  * (file.c:381-405).  Without a FILE, or for "-", the samples come from stdin
  * (read once, airspacecli.c:212-245) and go to stdout.
  *
- * MI355X-first: the reference compresses one file per call.  Here runs of
- * consecutive files of the same size (up to BATCH_BYTES) go to the GPU as
- * one cmp_gpu_compress() batch, which produces the same frames, in the same
+ * MI355X-first: the reference compresses one file per call.  Here consecutive
+ * files, of any sizes (up to BATCH_BYTES of samples), go to the GPU as they
+ * were read -- big-endian, back to back -- and are one
+ * cmp_gpu_compress_image() call, which produces the same frames, in the same
  * order and with the same context state, as one cmp_compress_u16() per file
- * (cmp_gpu.h).  Parameter sets that need a work buffer (MODEL or IWT) batch
- * the same way since round 5, with the work buffer on the device: the model
- * carries from one file to the next, inside a batch and across batches, as
- * in the reference's per-file loop (file.c:435-488).
+ * (cmp_gpu.h), packed as a .air image whose slices are the output files.
+ * Parameter sets that need a work buffer (MODEL or IWT) batch the same way,
+ * with the work buffer on the device: the model carries from one file to the
+ * next, inside a batch and across batches, as in the reference's per-file
+ * loop (file.c:435-488).
  *
  * Decompression (the reference's default mode prints "Decompression not
  * implemented yet", airspacecli.c:421-423) is an extension here: the frames
@@ -308,8 +310,8 @@ static char *with_suffix(const char *name)
 /* ---- device staging -------------------------------------------------------- */
 struct dev {
 	struct cmp_gpu_engine *eng;
-	void *src, *dst, *sizes;
-	size_t src_cap, dst_cap, sizes_cap;
+	void *src, *dst, *sizes, *offs;
+	size_t src_cap, dst_cap, sizes_cap, offs_cap;
 };
 
 static int dev_reserve(void **p, size_t *cap, size_t need)
@@ -351,6 +353,8 @@ static void dev_close(struct dev *d)
 		hipFree(d->dst);
 	if (d->sizes)
 		hipFree(d->sizes);
+	if (d->offs)
+		hipFree(d->offs);
 	if (d->eng)
 		cmp_gpu_engine_destroy(d->eng);
 	memset(d, 0, sizeof(*d));
@@ -390,56 +394,42 @@ static int emit(struct job *j, int i, const void *frame, uint32_t size, uint32_t
 	return r;
 }
 
-static void be16_to_host(uint16_t *dst, const uint8_t *src, size_t n)
+/* The files [i0, i0 + nf) as they were read, back to back in img (file i at
+ * offs[i], fbs[i] bytes of big-endian samples): one copy to the device, one
+ * cmp_gpu_compress_image() call, one read-back each of the sizes, the offsets
+ * and the packed image, whose slices are written out in order. */
+static int compress_batch(struct job *j, struct dev *d, struct cmp_context *ctx, int i0, uint32_t nf,
+			  const uint8_t *img, uint64_t img_len, const uint64_t *offs, const uint32_t *fbs)
 {
-	size_t i;
+	struct cmp_gpu_encode_image q;
+	uint64_t *out_offs, cap = 0;
+	uint32_t *sizes, e, i;
+	uint8_t *air = NULL;
+	int r = 0;
 
-	for (i = 0; i < n; i++)
-		dst[i] = (uint16_t)(src[2 * i] << 8 | src[2 * i + 1]);
-}
-
-static uint32_t frame_capacity(uint32_t src_size)
-{
-	uint32_t cap = cmp_compress_bound(src_size);
-
-	if (cmp_is_error(cap)) {
-		log_msg(LOG_WARNING, "Can't calculating compressed data buffer size, use maximum size");
-		cap = (1u << 24) - 1u;
-	}
-	return cap;
-}
-
-/* A run of same-size files [i0, i1) as one GPU batch (frames at a 16-byte
- * stride in stage), written out in order. */
-static int compress_run(struct job *j, struct dev *d, struct cmp_context *ctx, int i0, int i1, uint32_t size,
-			uint16_t *stage)
-{
-	const uint32_t nf = (uint32_t)(i1 - i0);
-	const uint32_t cap = frame_capacity(size);
-	const uint64_t dstride = ((uint64_t)cap + 7u) & ~7ull;
-	const uint64_t sstride = ((uint64_t)size + 15u) & ~15ull;
-	struct cmp_gpu_batch b;
-	uint32_t *sizes, e;
-	uint8_t *frame;
-	int i, r = 0;
-
-	if (dev_open(d) || dev_reserve(&d->src, &d->src_cap, sstride * nf) ||
-	    dev_reserve(&d->dst, &d->dst_cap, dstride * nf) || dev_reserve(&d->sizes, &d->sizes_cap, 4u * nf))
+	for (i = 0; i < nf; i++)
+		cap += cmp_compress_bound(fbs[i]);
+	if (dev_open(d) || dev_reserve(&d->src, &d->src_cap, img_len ? img_len : 16u) ||
+	    dev_reserve(&d->dst, &d->dst_cap, cap) || dev_reserve(&d->sizes, &d->sizes_cap, 4u * nf) ||
+	    dev_reserve(&d->offs, &d->offs_cap, 8u * ((size_t)nf + 1u)))
 		return -1;
-	if (hipMemcpy(d->src, stage, sstride * nf, hipMemcpyHostToDevice) != hipSuccess) {
+	if (img_len && hipMemcpy(d->src, img, img_len, hipMemcpyHostToDevice) != hipSuccess) {
 		log_msg(LOG_ERROR, "Copy to the GPU failed");
 		return -1;
 	}
-	memset(&b, 0, sizeof(b));
-	b.type = CMP_GPU_U16;
-	b.src = d->src;
-	b.src_stride = sstride;
-	b.src_size = size;
-	b.dst = d->dst;
-	b.dst_stride = dstride;
-	b.dst_capacity = cap;
-	b.sizes = d->sizes;
-	e = cmp_gpu_compress(d->eng, ctx, 1, nf, &b);
+	memset(&q, 0, sizeof(q));
+	q.type = CMP_GPU_U16;
+	q.src = d->src;
+	q.src_size = img_len;
+	q.offsets = offs;
+	q.frame_bytes = fbs;
+	q.num_frames = nf;
+	q.out = d->dst;
+	q.out_capacity = cap;
+	q.out_offsets = d->offs;
+	q.sizes = d->sizes;
+	q.flags = CMP_GPU_IMG_SRC_BIG_ENDIAN;
+	e = cmp_gpu_compress_image(d->eng, ctx, &q);
 	if (!cmp_is_error(e))
 		e = cmp_gpu_synchronize(d->eng);
 	if (cmp_is_error(e)) {
@@ -447,25 +437,87 @@ static int compress_run(struct job *j, struct dev *d, struct cmp_context *ctx, i
 		return -1;
 	}
 	sizes = xmalloc(4u * nf);
-	frame = xmalloc(cap);
-	if (hipMemcpy(sizes, d->sizes, 4u * nf, hipMemcpyDeviceToHost) != hipSuccess) {
+	out_offs = xmalloc(8u * ((size_t)nf + 1u));
+	if (hipMemcpy(sizes, d->sizes, 4u * nf, hipMemcpyDeviceToHost) != hipSuccess ||
+	    hipMemcpy(out_offs, d->offs, 8u * ((size_t)nf + 1u), hipMemcpyDeviceToHost) != hipSuccess) {
 		log_msg(LOG_ERROR, "Copy from the GPU failed");
 		r = -1;
 	}
-	for (i = 0; !r && i < (int)nf; i++) {
-		if (cmp_is_error(sizes[i])) {
-			log_cmp(sizes[i], "Compression failed for %s", display(j->in[i0 + i]));
-			r = -1;
-		} else if (hipMemcpy(frame, (uint8_t *)d->dst + dstride * i, sizes[i], hipMemcpyDeviceToHost) !=
-			   hipSuccess) {
+	if (!r && out_offs[nf]) {
+		air = xmalloc(out_offs[nf]);
+		if (hipMemcpy(air, d->dst, out_offs[nf], hipMemcpyDeviceToHost) != hipSuccess) {
 			log_msg(LOG_ERROR, "Copy from the GPU failed");
 			r = -1;
-		} else {
-			r = emit(j, i0 + i, frame, sizes[i], size);
 		}
 	}
-	free(frame);
+	for (i = 0; !r && i < nf; i++) {
+		if (cmp_is_error(sizes[i])) {
+			log_cmp(sizes[i], "Compression failed for %s", display(j->in[i0 + (int)i]));
+			r = -1;
+		} else {
+			r = emit(j, i0 + (int)i, air + out_offs[i], sizes[i], fbs[i]);
+		}
+	}
+	free(air);
+	free(out_offs);
 	free(sizes);
+	return r;
+}
+
+/* A file too large for cmp_compress_bound() (more than 5.59 MB of samples):
+ * the reference goes on with the largest frame a header can describe
+ * (file.c:424-430), which the image call's per-frame capacity cannot express.
+ * Such a file is a cmp_gpu_compress() batch of its own, from samples swapped
+ * here. */
+static int compress_oversize(struct job *j, struct dev *d, struct cmp_context *ctx, int i, const uint8_t *raw,
+			     uint32_t size)
+{
+	const uint32_t cap = (1u << 24) - 1u;
+	struct cmp_gpu_batch b;
+	uint16_t *x = xmalloc(size ? size : 2u);
+	uint8_t *frame = NULL;
+	uint32_t e, got = 0, k;
+	int r = -1;
+
+	log_msg(LOG_WARNING, "Can't calculating compressed data buffer size, use maximum size");
+	for (k = 0; k < size / 2u; k++)
+		x[k] = (uint16_t)(raw[2 * k] << 8 | raw[2 * k + 1]);
+	if (dev_open(d) || dev_reserve(&d->src, &d->src_cap, size) || dev_reserve(&d->dst, &d->dst_cap, cap + 1u) ||
+	    dev_reserve(&d->sizes, &d->sizes_cap, 4u))
+		goto out;
+	if (hipMemcpy(d->src, x, size, hipMemcpyHostToDevice) != hipSuccess) {
+		log_msg(LOG_ERROR, "Copy to the GPU failed");
+		goto out;
+	}
+	memset(&b, 0, sizeof(b));
+	b.type = CMP_GPU_U16;
+	b.src = d->src;
+	b.src_stride = size;
+	b.src_size = size;
+	b.dst = d->dst;
+	b.dst_stride = cap + 1u;
+	b.dst_capacity = cap;
+	b.sizes = d->sizes;
+	e = cmp_gpu_compress(d->eng, ctx, 1, 1, &b);
+	if (!cmp_is_error(e))
+		e = cmp_gpu_synchronize(d->eng);
+	if (!cmp_is_error(e) && hipMemcpy(&got, d->sizes, 4u, hipMemcpyDeviceToHost) != hipSuccess) {
+		log_msg(LOG_ERROR, "Copy from the GPU failed");
+		goto out;
+	}
+	if (cmp_is_error(e) || cmp_is_error(got)) {
+		log_cmp(cmp_is_error(e) ? e : got, "Compression failed for %s", display(j->in[i]));
+		goto out;
+	}
+	frame = xmalloc(got);
+	if (hipMemcpy(frame, d->dst, got, hipMemcpyDeviceToHost) != hipSuccess) {
+		log_msg(LOG_ERROR, "Copy from the GPU failed");
+		goto out;
+	}
+	r = emit(j, i, frame, got, size);
+out:
+	free(frame);
+	free(x);
 	return r;
 }
 
@@ -502,15 +554,15 @@ static int compress_files(struct job *j, const struct cmp_params *par)
 	}
 
 	{
-		/* batches of consecutive same-size files */
-		uint16_t *stage = NULL;
-		size_t stage_cap = 0;
-		int i0 = 0, nrun = 0;
-		uint32_t run_size = 0;
+		/* batches of consecutive files, of any sizes, as they are stored */
+		uint8_t *img = NULL;
+		uint64_t *offs = xmalloc((size_t)j->n_in * sizeof(*offs)), img_len = 0;
+		uint32_t *fbs = xmalloc((size_t)j->n_in * sizeof(*fbs)), nb = 0;
+		size_t img_cap = 0;
+		int i0 = 0, failed = 0;
 
-		for (i = 0; i <= j->n_in; i++) {
-			int load_failed = 0;
-			uint64_t sstride;
+		for (i = 0; i <= j->n_in && !failed; i++) {
+			int load_failed = 0, oversize = 0;
 
 			if (i < j->n_in) {
 				if (load_file(j->in[i], &raw, &size, &owned)) {
@@ -520,48 +572,53 @@ static int compress_files(struct job *j, const struct cmp_params *par)
 					if (owned)
 						free(raw);
 					load_failed = 1;
+				} else {
+					oversize = size > UINT32_MAX || cmp_is_error(cmp_compress_bound((uint32_t)size));
 				}
 			}
-			sstride = ((uint64_t)run_size + 15u) & ~15ull;
-			if (nrun && (i == j->n_in || load_failed || size != run_size ||
-				     sstride * (uint64_t)(nrun + 1) > BATCH_BYTES)) {
-				if (compress_run(j, &d, &ctx, i0, i0 + nrun, run_size, stage)) {
-					if (i < j->n_in && !load_failed && owned)
-						free(raw);
-					free(stage);
-					goto done;
-				}
-				nrun = 0;
+			if (nb && (i == j->n_in || load_failed || oversize || img_len + size > BATCH_BYTES)) {
+				failed = compress_batch(j, &d, &ctx, i0, nb, img, img_len, offs, fbs);
+				nb = 0;
+				img_len = 0;
 			}
 			if (i == j->n_in || load_failed) {
-				if (load_failed) {
-					free(stage);
-					goto done;
-				}
+				failed = failed || load_failed;
 				break;
 			}
-			if (!nrun) {
+			if (failed || oversize) {
+				if (!failed)
+					failed = compress_oversize(j, &d, &ctx, i, raw, (uint32_t)size);
+				if (owned)
+					free(raw);
+				continue;
+			}
+			if (!nb)
 				i0 = i;
-				run_size = (uint32_t)size;
-			}
-			sstride = ((uint64_t)run_size + 15u) & ~15ull;
-			if (sstride * (uint64_t)(nrun + 1) > stage_cap) {
-				size_t want = (size_t)(sstride * (uint64_t)(nrun + 1));
+			if (img_len + size > img_cap) {
+				size_t want = (size_t)(img_len + size);
 
-				want = want < 2 * stage_cap ? 2 * stage_cap : want;
-				stage = realloc(stage, want);
-				if (!stage) {
+				want = want < 2 * img_cap ? 2 * img_cap : want;
+				img = realloc(img, want);
+				if (!img) {
 					log_errno("Memory allocation failed");
-					goto done;
+					failed = 1;
 				}
-				stage_cap = want;
+				img_cap = want;
 			}
-			be16_to_host((uint16_t *)((uint8_t *)stage + sstride * nrun), raw, size / 2u);
+			if (!failed) {
+				memcpy(img + img_len, raw, size);
+				offs[nb] = img_len;
+				fbs[nb++] = (uint32_t)size;
+				img_len += size;
+			}
 			if (owned)
 				free(raw);
-			nrun++;
 		}
-		free(stage);
+		free(img);
+		free(offs);
+		free(fbs);
+		if (failed)
+			goto done;
 	}
 	log_summary("compressed", j->in, j->n_in, j->sum_in, j->last_out ? j->last_out : "", j->sum_out);
 	r = 0;

@@ -214,10 +214,11 @@ uint32_t airs_dev_synth(struct airs_dev_engine *e, void *dst, uint32_t sample_by
 			uint32_t W);
 
 /* engine-owned scratch, grown on demand (stream ordered) */
-#define AIRS_NSLOT 22 /* scratch slots per engine; the last five are the device layer's (checksum
+#define AIRS_NSLOT 25 /* scratch slots per engine; the last five are the device layer's (checksum
 		       * placement, checksum products, decoder parse arrays, decoder frame info, IWT heads) */
 #define AIRS_SLOT_GATHER 11 /* slots 11..13: cmp_gpu_gather (cmp_gather.c); 0..10 cmp_host.c */
 #define AIRS_SLOT_IMAGE 14 /* slots 14..16: airs_dev_decode_image (tables, staging rows, model) */
+#define AIRS_SLOT_ENCIMG 17 /* slots 17..19: cmp_gpu_compress_image (tables, sample rows, frame rows) */
 void *airs_dev_scratch(struct airs_dev_engine *e, int slot, size_t bytes);
 /* engine-owned device words for the gather's status exchanges (cmp_gather.c),
  * allocated with the engine so that taking part in an exchange never needs an
@@ -326,6 +327,64 @@ struct airs_decode_image {
 	uint64_t chunk_bytes;
 };
 uint32_t airs_dev_decode_image(struct airs_dev_engine *e, const struct airs_decode_image *q);
+
+/* sample images (cmp_gpu_compress_image, see cmp_gpu.h; encode_image.hip): the
+ * device work of one run of equal frames around the batch encoder, which the
+ * caller (cmp_encode_image.c) runs between the two stages.  Everything is
+ * queued on the engine's stream; nothing here synchronises.
+ *   AIRS_ENCIMG_INGEST  frame j's frame_bytes bytes at src + offsets[j] (any
+ *                       alignment) into the 16-byte aligned native row
+ *                       rows + j*row_bytes, zero up to the next multiple of 16,
+ *                       16-bit words byte-swapped with `swap`.
+ *   AIRS_ENCIMG_EMIT    the offset scan, then the copy.  With B = out_offsets[0]
+ *                       (0, written here, when first_run) and the sticky word
+ *                       (0 when first_run): out_offsets[j + 1] = out_offsets[j] +
+ *                       sizes[j], 0 for an error value; from the first frame
+ *                       whose end passes out_capacity on, the sticky word is set,
+ *                       every sizes[j] becomes CMP_ERR_DST_TOO_SMALL and the
+ *                       offsets stand still.  With `force` (an error value) no
+ *                       frame was encoded: every sizes[j] = force, no bytes.
+ *                       Then frame row j (frows + j*frow_bytes, sizes[j] bytes)
+ *                       goes to out + out_offsets[j]: whole 16-byte lines of out,
+ *                       heads and tails byte by byte. */
+enum airs_encimg_stage { AIRS_ENCIMG_INGEST = 0, AIRS_ENCIMG_EMIT = 1 };
+struct airs_encode_image {
+	uint32_t stage;
+	uint32_t count;           /* frames of the run */
+	/* ingest */
+	const void *src;
+	const uint64_t *offsets;  /* device [count] */
+	uint32_t frame_bytes;
+	uint32_t swap;
+	void *rows;               /* 16-byte aligned */
+	uint32_t row_bytes;       /* multiple of 16, >= frame_bytes rounded up to 16 */
+	/* emit */
+	const void *frows;        /* 8-byte aligned, readable up to 16 bytes past the last row */
+	uint32_t frow_bytes;      /* multiple of 8 */
+	uint32_t frow_cap;        /* the largest frame a row can hold */
+	uint32_t *sizes;          /* device [count] */
+	uint64_t *out_offsets;    /* device [count + 1] */
+	uint32_t *sticky;         /* device word */
+	void *out;
+	uint64_t out_capacity;
+	uint32_t first_run;
+	uint32_t force;
+};
+uint32_t airs_dev_encode_image(struct airs_dev_engine *e, const struct airs_encode_image *q);
+
+/* Host-side counters of the process, counted where the kernels are launched:
+ * frames that went through the ingest copy (a run read where it lies adds
+ * none), frames handed to the emit copy, frames of refused runs (the scan
+ * alone).  Copies the first min(n, AIRS_ENCIMG_STAT_COUNT) counters to out and
+ * returns AIRS_ENCIMG_STAT_COUNT.  For tests; nothing in the library reads
+ * them. */
+enum airs_encimg_stat {
+	AIRS_ENCIMG_STAT_INGEST = 0,
+	AIRS_ENCIMG_STAT_EMIT = 1,
+	AIRS_ENCIMG_STAT_REFUSED = 2,
+	AIRS_ENCIMG_STAT_COUNT = 3
+};
+uint32_t airs_dev_encode_image_stats(uint64_t *out, uint32_t n);
 
 /* payload-only stream (cmp_gpu_decode_stream, see cmp_gpu.h): the frame
  * pipeline over one "frame" described by the arguments instead of a header

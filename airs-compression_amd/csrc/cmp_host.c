@@ -1849,6 +1849,21 @@ static uint32_t batch_iwt(struct cmp_gpu_engine *eng, struct cmp_context *ctx, u
 uint32_t cmp_gpu_compress(struct cmp_gpu_engine *eng, struct cmp_context *ctx, uint32_t num_ctx,
 			  uint32_t fpc, const struct cmp_gpu_batch *b)
 {
+	return cmp_batch_compress(eng, ctx, num_ctx, fpc, b);
+}
+
+uint32_t cmp_context_usable(const struct cmp_context *ctx)
+{
+	if (ctx->magic != CTX_MAGIC)
+		return ERRV(CONTEXT_INVALID);
+	if (work_buf_state(&ctx->params) && ((uintptr_t)ctx->work_buf & 1u))
+		return ERRV(WORK_BUF_UNALIGNED);
+	return 0;
+}
+
+uint32_t cmp_batch_compress(struct cmp_gpu_engine *eng, struct cmp_context *ctx, uint32_t num_ctx, uint32_t fpc,
+			    const struct cmp_gpu_batch *b)
+{
 	const uint32_t bytes = b && b->type == CMP_GPU_I16_IN_I32 ? 4u : 2u;
 	uint32_t n, c, a, total, e = 0, any_model = 0, any_mneed = 0, exact = 0;
 	struct frame_plan *plan;

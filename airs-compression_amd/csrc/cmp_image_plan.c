@@ -1,9 +1,10 @@
 /*
  * cmp_image_plan.c -- the host side of cmp_gpu_decompress_image that needs no
  * device: cmp_gpu_frame_table (include/cmp_gpu.h), the walk over an image of
- * back-to-back frames, and the chunk planner.  Nothing here includes HIP or
- * the device layer, so a stand-alone program links this file alone
- * (tests/sanitize/image_plan_fuzz.c).
+ * back-to-back frames, and the chunk planner; and the run planner of
+ * cmp_gpu_compress_image.  Nothing here includes HIP or the device layer, so
+ * a stand-alone program links this file alone
+ * (tests/sanitize/image_plan_fuzz.c, encode_plan_fuzz.c).
  */
 #include <stddef.h>
 #include <stdint.h>
@@ -73,4 +74,28 @@ void cmp_image_plan_next(const uint32_t *frames, uint64_t num_frames, uint64_t b
 	chunk->src_cap = cap;
 	chunk->dst_samples = nmax;
 	chunk->dst_stride = up16(2u * nmax);
+}
+
+uint64_t cmp_image_run_row(uint32_t frame_bytes, uint32_t bound)
+{
+	return (((uint64_t)frame_bytes + 15u) & ~(uint64_t)15u) + (((uint64_t)bound + 7u) & ~(uint64_t)7u);
+}
+
+void cmp_image_run_next(const uint32_t *frame_bytes, uint64_t num_frames, uint64_t budget, uint64_t row_bytes,
+			uint32_t max_frames, uint64_t first, struct cmp_image_run *run)
+{
+	const uint32_t size = frame_bytes[first];
+	uint64_t count = 1, most;
+
+	if (!budget)
+		budget = CMP_IMAGE_CHUNK_DEFAULT;
+	if (!max_frames || max_frames > CMP_IMAGE_RUN_FRAMES)
+		max_frames = CMP_IMAGE_RUN_FRAMES;
+	most = row_bytes ? budget / row_bytes : max_frames;
+	if (most > max_frames)
+		most = max_frames;
+	while (count < most && first + count < num_frames && frame_bytes[first + count] == size)
+		count++;
+	run->first = first;
+	run->count = (uint32_t)count;
 }

@@ -1,5 +1,6 @@
-/* cmp_image_plan.h -- host planning of cmp_gpu_decompress_image (cmp_image_plan.c):
- * free of the device, so that a stand-alone program can link it. */
+/* cmp_image_plan.h -- host planning of cmp_gpu_decompress_image and
+ * cmp_gpu_compress_image (cmp_image_plan.c): free of the device, so that a
+ * stand-alone program can link it. */
 #ifndef CMP_IMAGE_PLAN_H
 #define CMP_IMAGE_PLAN_H
 
@@ -31,6 +32,28 @@ struct cmp_image_chunk {
  * count within CMP_IMAGE_CHUNK_FRAMES; it always takes one. */
 void cmp_image_plan_next(const uint32_t *frames, uint64_t num_frames, uint64_t budget, uint64_t first,
 			 struct cmp_image_chunk *chunk);
+
+#define CMP_IMAGE_RUN_FRAMES 0xFFFFFFFu /* frames per run at most: what one cmp_gpu_compress call accepts */
+
+/* one batch call of cmp_gpu_compress_image: frames [first, first + count), all
+ * of frame_bytes[first] bytes */
+struct cmp_image_run {
+	uint64_t first;
+	uint32_t count; /* 1 .. CMP_IMAGE_RUN_FRAMES */
+};
+
+/* the staging a frame of `frame_bytes` bytes of samples takes: its sample row
+ * (frame_bytes rounded up to 16) and its frame row (`bound`, the frame's
+ * cmp_compress_bound, rounded up to 8) */
+uint64_t cmp_image_run_row(uint32_t frame_bytes, uint32_t bound);
+
+/* The run that starts at frame `first` < num_frames: the maximal stretch of
+ * consecutive frames with frame_bytes[f] == frame_bytes[first], cut so that
+ * count * row_bytes (cmp_image_run_row of the run's frames) stays within
+ * `budget` (0: the default) and count within max_frames (0, or anything above
+ * it: CMP_IMAGE_RUN_FRAMES); it always takes one frame. */
+void cmp_image_run_next(const uint32_t *frame_bytes, uint64_t num_frames, uint64_t budget, uint64_t row_bytes,
+			uint32_t max_frames, uint64_t first, struct cmp_image_run *run);
 
 #ifdef __cplusplus
 }

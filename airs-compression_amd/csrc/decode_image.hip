@@ -34,12 +34,10 @@
 
 #include "airs_dev.h"
 #include "cmp_image_plan.h"
+#include "img_copy.h"
 
 namespace airsimg {
 
-#define IMG_WG 256u
-#define IMG_LINES 4u // 16-byte lines per lane
-#define IMG_TILE (IMG_WG * IMG_LINES * 16u)
 #define E_GENERIC 1u
 #define E_DST_TOO_SMALL 30u
 #define ERRV(c) ((uint32_t)0u - (uint32_t)(c))
@@ -76,45 +74,6 @@ __global__ void img_hdr_kernel(const uint8_t *src, uint64_t src_size, const uint
 	hdr[f] = r;
 }
 
-// The 16 bytes at s (any alignment, s < end) from the two aligned lines around
-// them.  The second line is requested only when it holds a byte below end, so
-// no load leaves the aligned hull of the bytes the caller owns; what it would
-// have held reads as zero.  The phase is the same for a whole workgroup (one
-// frame), so the switch is a uniform branch.
-__device__ __forceinline__ uint4 img_fetch16(const uint8_t *s, const uint8_t *end)
-{
-	const uintptr_t base = (uintptr_t)s & ~(uintptr_t)15u;
-	const uint32_t p = (uint32_t)((uintptr_t)s & 15u), bs = p & 3u;
-	const uint4 lo = *reinterpret_cast<const uint4 *>(base);
-	uint4 hi = make_uint4(0u, 0u, 0u, 0u);
-	if (p && base + 16u < (uintptr_t)end)
-		hi = *reinterpret_cast<const uint4 *>(base + 16u);
-#define IMG_AB(h, l) __builtin_amdgcn_alignbyte(h, l, bs)
-	switch (p >> 2) {
-	case 0:
-		return make_uint4(IMG_AB(lo.y, lo.x), IMG_AB(lo.z, lo.y), IMG_AB(lo.w, lo.z), IMG_AB(hi.x, lo.w));
-	case 1:
-		return make_uint4(IMG_AB(lo.z, lo.y), IMG_AB(lo.w, lo.z), IMG_AB(hi.x, lo.w), IMG_AB(hi.y, hi.x));
-	case 2:
-		return make_uint4(IMG_AB(lo.w, lo.z), IMG_AB(hi.x, lo.w), IMG_AB(hi.y, hi.x), IMG_AB(hi.z, hi.y));
-	default:
-		return make_uint4(IMG_AB(hi.x, lo.w), IMG_AB(hi.y, hi.x), IMG_AB(hi.z, hi.y), IMG_AB(hi.w, hi.z));
-	}
-#undef IMG_AB
-}
-
-// the first r (< 16) bytes of v, the rest zero
-__device__ __forceinline__ uint4 img_keep(uint4 v, uint32_t r)
-{
-	uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-	for (uint32_t k = 0; k < 4u; k++) {
-		const uint32_t keep = r > 4u * k ? min(r - 4u * k, 4u) : 0u;
-		w[k] = keep == 4u ? w[k] : w[k] & ((1u << (8u * keep)) - 1u);
-	}
-	return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // Grid: 16 KiB tiles of a row x frames of the chunk.
 __global__ __launch_bounds__(IMG_WG) void img_unpack_kernel(ImgArgs a)
 {
@@ -144,12 +103,6 @@ __global__ __launch_bounds__(IMG_WG) void img_unpack_kernel(ImgArgs a)
 		if (t < fill)
 			*reinterpret_cast<uint4 *>(row + t) = v[i];
 	}
-}
-
-// two 16-bit samples in a word, each byte-swapped
-__device__ __forceinline__ uint32_t img_swap16x2(uint32_t v)
-{
-	return __builtin_amdgcn_perm(v, v, 0x02030001u);
 }
 
 // Grid: 16 KiB tiles of a decoded row x frames of the chunk.  The frame's

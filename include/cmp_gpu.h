@@ -101,8 +101,9 @@ void cmp_gpu_engine_destroy(struct cmp_gpu_engine *engine);
  *                               they would take the context walk (not those
  *                               with the uncompressed fallback, which need it).
  *   CMP_GPU_OPT_IMAGE_CHUNK     (4, defined with cmp_gpu_decompress_image) bytes
- *                               of engine scratch a chunk of that call may
- *                               stage; 0: the default, 256 MiB. */
+ *                               of engine scratch a chunk of that call, or a run
+ *                               of cmp_gpu_compress_image, may stage; 0: the
+ *                               default, 256 MiB. */
 #define CMP_GPU_OPT_EXCLUSIVE 1u
 #define CMP_GPU_OPT_WALK_SEGMENT 2u
 #define CMP_GPU_OPT_NO_CONTEXT_WALK 3u
@@ -296,6 +297,92 @@ uint32_t cmp_gpu_decompress_image(struct cmp_gpu_engine *engine, const struct cm
  * written. */
 uint64_t cmp_gpu_frame_table(const void *image, uint64_t size, uint64_t *offsets, uint64_t max_frames,
 			     uint64_t *bad_at);
+
+/*
+ * Sample images: the mirror of cmp_gpu_decompress_image.  Sample frames as
+ * they are stored -- at any byte offset of ONE device buffer, of unequal
+ * sizes, optionally big-endian as the sample files hold them -- compressed as
+ * one context in one call into a .air image on the device: the frames back to
+ * back at byte granularity, with their offset table.
+ *
+ * Equivalence.  The frames are one context, in table order; the call is
+ * equivalent to
+ *
+ *     for f in [0, num_frames):
+ *         sizes[f] = cmp_compress_<type>(ctx, tmp_f, cmp_compress_bound(frame_bytes[f]),
+ *                                        native(src + offsets[f]), frame_bytes[f])
+ *
+ * with all of the loop's effects: the timestamp-callback sequence, the
+ * context's final sequence number, identifier and model size, and the work
+ * buffer (a DEVICE pointer, as for cmp_gpu_compress).  Per-frame errors land in
+ * sizes[f] with the value the loop gives: a size change in a MODEL context
+ * CMP_ERR_SRC_SIZE_MISMATCH (cmp.c:246), a frame_bytes of 0 or no multiple of
+ * the sample size CMP_ERR_SRC_SIZE_WRONG, a work buffer that is too small
+ * CMP_ERR_WORK_BUF_TOO_SMALL, a frame_bytes whose cmp_compress_bound is an
+ * error value CMP_ERR_GENERIC (cmp.c:350).  An errored frame takes no bytes.
+ *
+ * Layout.  out_offsets[0] = 0 and out_offsets[f + 1] = out_offsets[f] + (0 if
+ * sizes[f] is an error value, else sizes[f]); frame f's bytes are at
+ * out + out_offsets[f], nothing between the frames.  cmp_gpu_frame_table over
+ * the first out_offsets[num_frames] bytes (read back) finds exactly the
+ * stored frames.
+ *
+ * Capacity.  A frame whose end would pass out_capacity is not stored and gets
+ * CMP_ERR_DST_TOO_SMALL, and so does EVERY frame after it, whatever its own
+ * outcome was, so the image is always a prefix of the full result.  The
+ * context ends as if all frames had fitted: this is the one place where the
+ * call differs from a loop that ran into a small dst.  Nothing is written
+ * outside [out, out + out_offsets[num_frames]).
+ *
+ * Reads.  No byte outside the 16-byte aligned hull of [src, src + src_size)
+ * is read.
+ *
+ * Returns CMP_ERR_NO_ERROR or a call-level refusal, raised before anything
+ * reaches the device, checked in this order: NULL engine, ctx, img, offsets,
+ * frame_bytes, out_offsets or sizes, or num_frames 0: CMP_ERR_GENERIC; NULL
+ * src CMP_ERR_SRC_NULL; src_size 0, or an offsets[f] + frame_bytes[f] above
+ * src_size, CMP_ERR_SRC_SIZE_WRONG; NULL out CMP_ERR_DST_NULL; out_offsets not
+ * 8-byte or sizes not 4-byte aligned, an unknown type, flag or batch flag,
+ * CMP_GPU_REPORT_DRAWS among the batch flags, CMP_GPU_IMG_SRC_BIG_ENDIAN with
+ * CMP_GPU_I16_IN_I32: CMP_ERR_GENERIC; then the context as cmp_gpu_compress
+ * refuses it: CMP_ERR_CONTEXT_INVALID, or CMP_ERR_WORK_BUF_UNALIGNED for an odd
+ * work buffer of a context that keeps state there.
+ *
+ * The table is cut into runs: maximal stretches of consecutive frames of equal
+ * frame_bytes, cut further so that a run's staging rows fit
+ * CMP_GPU_OPT_IMAGE_CHUNK bytes of engine scratch (0: 256 MiB; a run always
+ * holds one frame at least; the result does not depend on the value).  Every
+ * run is one cmp_gpu_compress batch of one context (frames that all differ in
+ * size cost one launch each).  A run whose samples are native-endian, whose
+ * first frame is aligned to the sample size and whose offsets step by a
+ * constant that is at least frame_bytes and a multiple of the sample size is
+ * read where it is; every other run is first copied into aligned native rows.
+ *
+ * Synchronisation.  The call is asynchronous on the engine's stream exactly
+ * where cmp_gpu_compress with dst_capacity = cmp_compress_bound would be for
+ * each run, synchronises where that call does and nowhere else (engine scratch
+ * that has to grow waits for the stream, as there); sizes, out_offsets and out
+ * are valid after cmp_gpu_synchronize.  Build-defined extension.
+ */
+#define CMP_GPU_IMG_SRC_BIG_ENDIAN 0x1u /* samples in src are big-endian 16-bit words (sample files) */
+
+struct cmp_gpu_encode_image {
+	enum cmp_gpu_sample_type type;
+	const void *src;             /* device, ANY alignment */
+	uint64_t src_size;           /* bytes of the sample image */
+	const uint64_t *offsets;     /* HOST [num_frames]: byte offset of frame f's samples, any alignment,
+				      * any order, overlaps allowed; read during the call only */
+	const uint32_t *frame_bytes; /* HOST [num_frames]: frame f's src_size as cmp_compress_* takes it */
+	uint32_t num_frames;         /* >= 1, no 65535 limit (the call cuts runs) */
+	void *out;                   /* device, any alignment: the .air image */
+	uint64_t out_capacity;       /* bytes */
+	uint64_t *out_offsets;       /* DEVICE [num_frames + 1], 8-byte aligned */
+	uint32_t *sizes;             /* DEVICE [num_frames], 4-byte aligned: frame size or error value */
+	uint32_t batch_flags;        /* CMP_GPU_AUTO_RICE | HOST_STEPPED | STEPWISE, as cmp_gpu_batch.flags */
+	uint32_t flags;              /* CMP_GPU_IMG_SRC_BIG_ENDIAN */
+};
+uint32_t cmp_gpu_compress_image(struct cmp_gpu_engine *engine, struct cmp_context *ctx,
+				const struct cmp_gpu_encode_image *img);
 
 /*
  * Payload-only stream: the num_samples samples at src (device) encoded as ONE
