@@ -415,7 +415,10 @@ uint32_t airs_dev_d2d_rows(struct airs_dev_engine *e, void *dst, size_t dpitch, 
 /* Host-side launch counters of the process (every engine, every thread),
  * counted where the kernel is launched: which kernel family and look-back
  * mode a call took.  Copies the first min(n, AIRS_STAT_COUNT) counters to out
- * and returns AIRS_STAT_COUNT.  For tests; nothing in the library reads them. */
+ * and returns how many that is: counters are only ever added at the end, so a
+ * caller that knows the first n of them gets n whatever the library has since
+ * gained, and one that asks for more than the library has sees that it got
+ * fewer.  For tests; nothing in the library reads them. */
 enum airs_launch_stat {
 	AIRS_STAT_RICE_FRAME_LB1 = 0, /* rice_kernel, frames, lbmode bit 0 set (scalar look-back from sif 16) */
 	AIRS_STAT_RICE_FRAME_LB0 = 1, /* rice_kernel, frames, lbmode 0 (vector look-back) */
@@ -423,7 +426,8 @@ enum airs_launch_stat {
 	AIRS_STAT_RICE_AUTO = 3,      /* rice_kernel with the candidate barrier (CMP_GPU_AUTO_RICE) */
 	AIRS_STAT_ENCODE = 4,         /* encode_kernel, frames (its fused AUTO form included) */
 	AIRS_STAT_ENCODE_STREAM = 5,  /* encode_kernel, payload-only stream */
-	AIRS_STAT_COUNT = 6
+	AIRS_STAT_DECODE_ROUND = 6,   /* dec_parse_kernel, a settle round (first == 0); not the speculative launch */
+	AIRS_STAT_COUNT = 7
 };
 uint32_t airs_dev_launch_stats(uint64_t *out, uint32_t n);
 

@@ -32,6 +32,10 @@
 
 #include "airs_dev.h"
 
+namespace airs {
+void launch_count(uint32_t which); // encode.hip: the host-side launch counters (airs_dev_launch_stats)
+}
+
 namespace airsdec {
 
 #ifndef DEC_B
@@ -1104,6 +1108,7 @@ static uint32_t decode_frames(struct airs_dev_engine *e, const void *src, uint64
 		for (uint32_t round = 1; round <= a.mwg + 1u; round++) {
 			DCHECK(hipMemsetAsync(a.changed, 0, 4, s));
 			hipLaunchKernelGGL(dec_parse_kernel, grid, dim3(DEC_WG), 0, s, a, (const uint32_t *)ein, eout, 0u);
+			airs::launch_count(AIRS_STAT_DECODE_ROUND);
 			uint32_t *tmp = ein;
 			ein = eout;
 			eout = tmp;

@@ -1175,9 +1175,10 @@ void launch_count(uint32_t which)
 } // namespace airs
 extern "C" uint32_t airs_dev_launch_stats(uint64_t *out, uint32_t n)
 {
-	for (uint32_t i = 0; out && i < n && i < AIRS_STAT_COUNT; i++)
+	const uint32_t m = n < AIRS_STAT_COUNT ? n : (uint32_t)AIRS_STAT_COUNT;
+	for (uint32_t i = 0; out && i < m; i++)
 		out[i] = g_launch_stats[i].load(std::memory_order_relaxed);
-	return AIRS_STAT_COUNT;
+	return m; // a caller that knows fewer counters gets the ones it knows
 }
 
 static uint32_t hip_fail(hipError_t e, const char *what)

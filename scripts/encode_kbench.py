@@ -18,7 +18,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 
 G, ROT, SPANS, PER_SPAN = 256, 3, 5, 20
-STATS = ("rice_lb1", "rice_lb0", "rice_stream", "rice_auto", "encode", "encode_stream")  # airs_dev.h airs_launch_stat
+STATS = ("rice_lb1", "rice_lb0", "rice_stream", "rice_auto", "encode", "encode_stream",
+         "decode_round")  # airs_dev.h airs_launch_stat
 pkg = bench.load_pkg()
 api = pkg.cmpapi
 lib = pkg.load()

@@ -16,8 +16,8 @@ SEG = 16384  # samples per segment of the Rice kernel
 HDR = 22     # bytes of a GOLOMB_ZERO frame header
 
 # airs_dev.h enum airs_launch_stat
-LB1, LB0, RICE_STREAM, RICE_AUTO, ENCODE, ENCODE_STREAM = range(6)
-STAT_NAMES = ("rice_lb1", "rice_lb0", "rice_stream", "rice_auto", "encode", "encode_stream")
+LB1, LB0, RICE_STREAM, RICE_AUTO, ENCODE, ENCODE_STREAM, DECODE_ROUND = range(7)
+STAT_NAMES = ("rice_lb1", "rice_lb0", "rice_stream", "rice_auto", "encode", "encode_stream", "decode_round")
 
 
 def launch_stats(prod):
