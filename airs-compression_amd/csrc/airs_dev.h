@@ -427,7 +427,10 @@ enum airs_launch_stat {
 	AIRS_STAT_ENCODE = 4,         /* encode_kernel, frames (its fused AUTO form included) */
 	AIRS_STAT_ENCODE_STREAM = 5,  /* encode_kernel, payload-only stream */
 	AIRS_STAT_DECODE_ROUND = 6,   /* dec_parse_kernel, a settle round (first == 0); not the speculative launch */
-	AIRS_STAT_COUNT = 7
+	AIRS_STAT_WALK_CTX = 7,       /* walk_ctx_kernel: MODEL contexts, one workgroup per context (fallback on the chip) */
+	AIRS_STAT_WALK_SEG = 8,       /* walk_kernel: MODEL contexts, the segment walk */
+	AIRS_STAT_FB_STEP = 9,        /* fb_step_kernel: a step of the per-acquisition device state machine */
+	AIRS_STAT_COUNT = 10
 };
 uint32_t airs_dev_launch_stats(uint64_t *out, uint32_t n);
 

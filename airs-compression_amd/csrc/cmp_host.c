@@ -407,6 +407,39 @@ static uint64_t model_fail_bit(uint32_t cap, uint32_t n)
 	return 64ull * (cap / 8u) + 63ull;
 }
 
+/* Longest codeword of a pass: 16 raw bits; GOLOMB_ZERO k + 17 with k =
+ * floor(log2 g) (the escape, and the longest code below the outlier,
+ * encoder.c:154-182; CMP_GPU_AUTO_RICE selects k up to 15); otherwise the
+ * reference's own bound of 48 bits (encoder.c:381-386). */
+static uint32_t pass_max_bits(uint32_t enc, uint32_t g, int auto_rice)
+{
+	uint32_t k = 0;
+
+	if (enc == CMP_ENCODER_UNCOMPRESSED)
+		return 16u;
+	if (enc != CMP_ENCODER_GOLOMB_ZERO || !g)
+		return 48u;
+	if (auto_rice)
+		return 32u;
+	while ((2u << k) <= g)
+		k++;
+	return k + 17u;
+}
+
+/* can a frame of n samples of this context exceed the 24-bit size field? */
+static int size_field_can_overflow(const struct cmp_params *P, uint32_t n, uint32_t flags)
+{
+	uint32_t bits = pass_max_bits(P->primary_encoder_type, P->primary_encoder_param,
+				      (flags & CMP_GPU_AUTO_RICE) != 0);
+
+	if (P->secondary_iterations) {
+		const uint32_t s = pass_max_bits(P->secondary_encoder_type, P->secondary_encoder_param, 0);
+
+		bits = s > bits ? s : bits;
+	}
+	return HDR_MAX_SIZE + CMP_CHECKSUM_SIZE + ((uint64_t)n * bits + 7u) / 8u > CMP_HDR_MAX_COMPRESSED_SIZE;
+}
+
 /* largest possible frame for n samples: header + 48 bits/sample + checksum */
 static uint64_t frame_worst(uint32_t n)
 {
@@ -1952,12 +1985,18 @@ uint32_t cmp_batch_compress(struct cmp_gpu_engine *eng, struct cmp_context *ctx,
 	 * size field (n > ~2.8 Mi samples: HDR_CMP_SIZE_TOO_LARGE is possible)
 	 * when a context has secondary passes.  Without secondary passes every
 	 * frame is a primary pass with one identifier draw whatever the outcome
-	 * of the frame before, so the plan does not depend on it. */
+	 * of the frame before, so the plan does not depend on it; the context's
+	 * sequence number after the call still does (a context whose last frame
+	 * fails stays at 0, cmp.c:321-338, and with secondary passes the next
+	 * call's first pass follows from it), so a batch whose coder can take a
+	 * frame past the size field runs step by step as well.  A coder whose
+	 * longest codeword keeps every frame within the field (cfg2's g = 32 at
+	 * 4 Mi samples: 22 bits per sample) cannot fail and stays asynchronous. */
 	if ((uint64_t)b->dst_capacity < HDR_MAX_SIZE + CMP_CHECKSUM_SIZE + payload_bound(2u * n))
 		exact = 1;
-	if (is_err(cmp_compress_bound(2u * n)) && fpc > 1)
+	if (is_err(cmp_compress_bound(2u * n)))
 		for (c = 0; c < num_ctx; c++)
-			if (ctx[c].params.secondary_iterations)
+			if ((ctx[c].params.secondary_iterations && fpc > 1) || size_field_can_overflow(&ctx[c].params, n, b->flags))
 				exact = 1;
 	if (!exact) {
 		/* replay the context state machine in call order (c-major), counting

@@ -1964,6 +1964,7 @@ extern "C" uint32_t airs_dev_walk(struct airs_dev_engine *e, struct airs_walk *w
 			kc.img_words = cw;
 			if (!walk_ctx_encode(kc, w->sample_bytes, w->pre_p, w->enc_p, true, w->enc_s, true, e->stream))
 				return ERRV(E_PARAMS_INVALID);
+			launch_count(AIRS_STAT_WALK_CTX);
 			HIPCHECK(hipGetLastError());
 			return 0;
 		}
@@ -1991,6 +1992,7 @@ extern "C" uint32_t airs_dev_walk(struct airs_dev_engine *e, struct airs_walk *w
 
 	if (wr < 0)
 		return ERRV(E_PARAMS_INVALID);
+	launch_count(AIRS_STAT_WALK_SEG);
 	HIPCHECK(hipGetLastError());
 	if (wr == 0) // the launch took tickets
 		e->walk_ticket_base += (uint32_t)(w->num_ctx * spf);
@@ -2155,6 +2157,7 @@ extern "C" uint32_t airs_dev_fb_step(struct airs_dev_engine *e, const struct air
 	if (!e || !s || !s->num_ctx)
 		return ERRV(E_GENERIC);
 	hipLaunchKernelGGL(fb_step_kernel, dim3((s->num_ctx + 255u) / 256u), dim3(256), 0, e->stream, *s);
+	launch_count(AIRS_STAT_FB_STEP);
 	HIPCHECK(hipGetLastError());
 	return 0;
 }

@@ -120,8 +120,12 @@ uint32_t cmp_gpu_engine_set_option(struct cmp_gpu_engine *engine, uint32_t optio
  * back to raw storage, and -- where that worst case exceeds the 24-bit
  * compressed-size field (more than ~2.8 Mi samples, so a frame can fail with
  * CMP_ERR_HDR_CMP_SIZE_TOO_LARGE) -- no context has secondary passes with
- * frames_per_ctx > 1.  Otherwise the outcome of frame (c, a) decides the pass
- * of frame (c, a+1), so the call runs one acquisition step at a time and
+ * frames_per_ctx > 1, and no context's coder can take a frame of this length
+ * past the field at its longest codeword (16 bits UNCOMPRESSED, k + 17 bits
+ * GOLOMB_ZERO with k = floor(log2 g), 48 bits otherwise), since a context
+ * whose last frame fails keeps its sequence number.  Otherwise the outcome
+ * of frame (c, a) decides the pass of frame (c, a+1) or the state the context
+ * is left in, so the call runs one acquisition step at a time and
  * synchronises after each step (and after the step's fallbacks,
  * cmp.c:342-393).  Identifier draws are counted per frame and made at the
  * end, in the loop's order.

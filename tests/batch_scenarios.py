@@ -60,12 +60,15 @@ def _calls(fpc, splits):
     return out
 
 
-def run_batch_host(lib, api, params, kind, n, nctx, fpc, cap, srcs, ts_start=5000, primary_g=None, splits=None):
+def run_batch_host(lib, api, params, kind, n, nctx, fpc, cap, srcs, ts_start=5000, primary_g=None, splits=None,
+                   tails=False):
     """primary_g: optional src -> g, set as the context's primary encoder
     parameter before each call (the CMP_GPU_AUTO_RICE rule).  splits: the
     acquisitions per cmp_gpu_compress call when the GPU side makes several
     calls on the same contexts (the loop order is then call by call, c-major
-    inside a call); frames are returned in (context, acquisition) order."""
+    inside a call); frames are returned in (context, acquisition) order.
+    tails: a third return value as run_batch_gpu's, the frames whose
+    destination lost its 0xAB fill at or behind the capacity."""
     sb = 4 if kind == "i16_in_i32" else 2
     pcs = _per_ctx(params, nctx)
     lib.set_timestamp_func(_ts_counter(ts_start))
@@ -78,6 +81,7 @@ def run_batch_host(lib, api, params, kind, n, nctx, fpc, cap, srcs, ts_start=500
             r = lib.initialise(ctxs[c], pcs[c], wbs_bufs[c] if w else None, w)
             assert not api.is_error(r), api.error_name(r)
         frames = [None] * (nctx * fpc)
+        dirty = []
         for a0, k in _calls(fpc, splits):
             for c in range(nctx):
                 for a in range(a0, a0 + k):
@@ -86,17 +90,25 @@ def run_batch_host(lib, api, params, kind, n, nctx, fpc, cap, srcs, ts_start=500
                         ctxs[c].params.primary_encoder_param = primary_g(srcs[c * fpc + a])
                     r = lib.compress(kind, ctxs[c], dst, cap, srcs[c * fpc + a])
                     frames[c * fpc + a] = (r, bytes(dst[:r]) if not api.is_error(r) else None)
+                    if tails and (dst[cap:] != 0xAB).any():
+                        dirty.append((c * fpc + a, cap + int(np.argmax(dst[cap:] != 0xAB))))
         state = [(x.identifier, x.sequence_number, x.model_size, bytes(w[:wbs]))
                  for x, w in zip(ctxs, wbs_bufs)]
+        if tails:
+            return tuple(frames), tuple(state), dirty
         return tuple(frames), tuple(state)
     finally:
         lib.set_timestamp_func(None)
 
 
 def run_batch_gpu(lib, eng, api, params, kind, n, nctx, fpc, cap, srcs, ts_start=5000, flags=0, splits=None,
-                  separate_work=False):
+                  separate_work=False, tails=False):
     """separate_work: each context's work buffer its own allocation, at
-    uneven distances (the library then passes a pointer per context)."""
+    uneven distances (the library then passes a pointer per context).
+    tails: a third return value, the destination rows written at or behind
+    the capacity: (frame, offset of the first byte that lost its 0xAB fill in
+    [cap, row end)) for every such row, of frames that fit and frames that do
+    not; empty when nothing was written there."""
     import torch
     sb = 4 if kind == "i16_in_i32" else 2
     pcs = _per_ctx(params, nctx)
@@ -143,6 +155,10 @@ def run_batch_gpu(lib, eng, api, params, kind, n, nctx, fpc, cap, srcs, ts_start
             frames[f] = (s, bytes(host[j * dstride:j * dstride + s]) if not api.is_error(s) else None)
         state = [(ctxs[c].identifier, ctxs[c].sequence_number, ctxs[c].model_size, bytes(wk[c]))
                  for c in range(nctx)]
+        if tails:
+            rows = host.reshape(nf, dstride)[:, cap:] != 0xAB
+            dirty = [(order[j], cap + int(np.argmax(rows[j]))) for j in range(nf) if rows[j].any()]
+            return tuple(frames), tuple(state), dirty
         return tuple(frames), tuple(state)
     finally:
         lib.set_timestamp_func(None)

@@ -127,7 +127,8 @@ def test_ladder_frames(orc, orc_ext):
 
 def test_launch_stats_serve_a_caller_that_knows_fewer_counters(prod):
     """airs_dev_launch_stats returns how many counters it copied: the six a
-    caller from before AIRS_STAT_DECODE_ROUND asks for, never more than the
+    caller from before AIRS_STAT_DECODE_ROUND asks for, the seven one from
+    before the walk and fallback-step counters asks for, never more than the
     library has, and nothing behind them in the caller's array."""
     import ctypes
     from rice_helpers import STAT_NAMES
@@ -135,8 +136,8 @@ def test_launch_stats_serve_a_caller_that_knows_fewer_counters(prod):
     fn.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32]
     fn.restype = ctypes.c_uint32
     have = len(STAT_NAMES)
-    assert have == 7
-    for n in (0, 1, 6, have, have + 5):
+    assert have == 10
+    for n in (0, 1, 6, 7, have, have + 5):
         out = (ctypes.c_uint64 * (have + 6))(*([2**64 - 1] * (have + 6)))
         got = fn(out, n)
         assert got == min(n, have), (n, got)
