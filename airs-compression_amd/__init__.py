@@ -33,6 +33,8 @@ OPT_IMAGE_CHUNK = 4  # CMP_GPU_OPT_IMAGE_CHUNK: bytes of staging per chunk of de
 IMG_MODEL_IN = 0x1  # CMP_GPU_IMG_MODEL_IN (cmp_gpu_decompress_image)
 IMG_BIG_ENDIAN = 0x2  # CMP_GPU_IMG_BIG_ENDIAN
 IMG_SRC_BIG_ENDIAN = 0x1  # CMP_GPU_IMG_SRC_BIG_ENDIAN (cmp_gpu_compress_image)
+ESTIMATE_MAX_CANDIDATES = 64  # CMP_GPU_ESTIMATE_MAX_CANDIDATES
+ESTIMATE_MAX_FRAMES = 1 << 20  # CMP_GPU_ESTIMATE_MAX_FRAMES
 KIND_TO_GPU = {"u16": GPU_U16, "i16": GPU_I16, "i16_in_i32": GPU_I16_IN_I32}
 
 
@@ -156,6 +158,45 @@ class GpuEncodeImage(ctypes.Structure):
     ]
 
 
+class GpuCandidate(ctypes.Structure):
+    """struct cmp_gpu_candidate (include/cmp_gpu.h): one pass's parameters."""
+    _fields_ = [
+        ("preprocessing", c_int),
+        ("encoder_type", c_int),
+        ("encoder_param", c_uint32),
+        ("encoder_outlier", c_uint32),
+    ]
+
+
+class GpuEstimateBatch(ctypes.Structure):
+    """struct cmp_gpu_estimate_batch (include/cmp_gpu.h)."""
+    _fields_ = [
+        ("type", c_int),
+        ("src", c_void_p),
+        ("src_stride", c_uint64),
+        ("src_size", c_uint32),
+        ("num_frames", c_uint32),
+        ("model", c_void_p),
+        ("model_stride", c_uint64),
+        ("candidates", POINTER(GpuCandidate)),
+        ("num_candidates", c_uint32),
+        ("bits", c_void_p),
+        ("best", c_void_p),
+        ("flags", c_uint32),
+    ]
+
+
+def candidate_array(candidates):
+    """A ctypes GpuCandidate array from GpuCandidate objects or (preprocessing,
+    encoder_type, encoder_param[, encoder_outlier]) tuples."""
+    arr = (GpuCandidate * max(len(candidates), 1))()
+    for i, c in enumerate(candidates):
+        if isinstance(c, GpuCandidate):
+            c = (c.preprocessing, c.encoder_type, c.encoder_param, c.encoder_outlier)
+        arr[i] = GpuCandidate(*c)
+    return arr
+
+
 class AirsLib(CmpLib):
     """CmpLib plus the cmp_gpu.h device batch API."""
 
@@ -202,6 +243,10 @@ class AirsLib(CmpLib):
         L.cmp_gpu_compress_image.restype = c_uint32
         L.cmp_gpu_frame_table.argtypes = [c_void_p, c_uint64, c_void_p, c_uint64, POINTER(c_uint64)]
         L.cmp_gpu_frame_table.restype = c_uint64
+        L.cmp_gpu_estimate.argtypes = [c_void_p, POINTER(GpuEstimateBatch)]
+        L.cmp_gpu_estimate.restype = c_uint32
+        L.cmp_gpu_estimate_frame_size.argtypes = [POINTER(GpuCandidate), c_uint64, c_int]
+        L.cmp_gpu_estimate_frame_size.restype = c_uint32
 
     def gpu_available(self) -> bool:
         return bool(self.lib.cmp_gpu_available())
@@ -238,6 +283,13 @@ class AirsLib(CmpLib):
         offs = np.zeros(max(room, 1), dtype=np.uint64)
         self.lib.cmp_gpu_frame_table(ptr, img.size, offs.ctypes.data, room, ctypes.byref(bad))
         return count, offs[:min(room, count)], (None if bad.value == 2 ** 64 - 1 else int(bad.value))
+
+    def estimate_frame_size(self, candidate, bits: int, checksum_enabled) -> int:
+        """cmp_gpu_estimate_frame_size (no device): the size of the frame that holds
+        `bits` payload bits coded with `candidate` (a GpuCandidate or a tuple, see
+        candidate_array), or an error value."""
+        c = None if candidate is None else candidate_array([candidate])
+        return int(self.lib.cmp_gpu_estimate_frame_size(c, bits, 1 if checksum_enabled else 0))
 
     def engine(self, stream: int | None = None) -> "GpuEngine":
         return GpuEngine(self, stream)
@@ -359,6 +411,20 @@ class GpuEngine:
         return self.lib.lib.cmp_gpu_decode_stream(self.handle, src_ptr or None, src_size, num_samples, preprocessing,
                                                   encoder_type, encoder_param, encoder_outlier, dst_ptr or None,
                                                   status_ptr or None)
+
+    def estimate(self, kind: str, src_ptr: int, src_stride: int, src_size: int, num_frames: int, candidates,
+                 bits_ptr: int, best_ptr: int = 0, model_ptr: int = 0, model_stride: int = 0) -> int:
+        """cmp_gpu_estimate over device pointers: bits[f * len(candidates) + c]
+        (uint64) = the payload bits of frame f under candidate c, best[f]
+        (uint32, optional) = the candidate of the smallest frame; both valid
+        after synchronize.  candidates: GpuCandidate objects or tuples (see
+        candidate_array)."""
+        arr = candidates if isinstance(candidates, ctypes.Array) else candidate_array(candidates)
+        b = GpuEstimateBatch(type=KIND_TO_GPU[kind], src=src_ptr or None, src_stride=src_stride, src_size=src_size,
+                             num_frames=num_frames, model=model_ptr or None, model_stride=model_stride,
+                             candidates=arr, num_candidates=len(candidates), bits=bits_ptr or None,
+                             best=best_ptr or None, flags=0)
+        return int(self.lib.lib.cmp_gpu_estimate(self.handle, ctypes.byref(b)))
 
     def pack_frames(self, frames_ptr: int, frame_stride: int, frame_capacity: int, sizes_ptr: int,
                     num_frames: int, out_ptr: int, offsets_ptr: int) -> int:

@@ -214,11 +214,12 @@ uint32_t airs_dev_synth(struct airs_dev_engine *e, void *dst, uint32_t sample_by
 			uint32_t W);
 
 /* engine-owned scratch, grown on demand (stream ordered) */
-#define AIRS_NSLOT 25 /* scratch slots per engine; the last five are the device layer's (checksum
+#define AIRS_NSLOT 27 /* scratch slots per engine; the last five are the device layer's (checksum
 		       * placement, checksum products, decoder parse arrays, decoder frame info, IWT heads) */
 #define AIRS_SLOT_GATHER 11 /* slots 11..13: cmp_gpu_gather (cmp_gather.c); 0..10 cmp_host.c */
 #define AIRS_SLOT_IMAGE 14 /* slots 14..16: airs_dev_decode_image (tables, staging rows, model) */
 #define AIRS_SLOT_ENCIMG 17 /* slots 17..19: cmp_gpu_compress_image (tables, sample rows, frame rows) */
+#define AIRS_SLOT_ESTIMATE 20 /* slots 20..21: airs_dev_estimate (slice partials, IWT coefficients) */
 void *airs_dev_scratch(struct airs_dev_engine *e, int slot, size_t bytes);
 /* engine-owned device words for the gather's status exchanges (cmp_gather.c),
  * allocated with the engine so that taking part in an exchange never needs an
@@ -400,6 +401,57 @@ uint32_t airs_dev_encode_image_stats(uint64_t *out, uint32_t n);
 uint32_t airs_dev_decode_stream(struct airs_dev_engine *e, const void *src, uint32_t src_size, uint32_t n,
 				uint32_t preprocessing, uint32_t encoder_type, uint32_t g, uint32_t outlier,
 				uint16_t *dst, uint32_t *status);
+
+/* the IWT coefficients of L's frames into L->model (the model addressing of the
+ * launch), as ahead of an IWT encode launch: what airs_dev_estimate sizes */
+uint32_t airs_dev_iwt(struct airs_dev_engine *e, const struct airs_launch *L);
+
+/* sizing (cmp_gpu_estimate, see cmp_gpu.h; estimate.hip): bits[f * num_cand + c]
+ * = the payload bits of frame f under candidate c, best[f] (optional) = the c
+ * that minimises 8 * hdr + bits, ties to the lowest c.  The candidates come
+ * resolved (cmp_estimate.c): everything is validated by the caller.  Queued on
+ * the engine's stream; nothing synchronises unless scratch has to grow. */
+enum airs_est_kind {
+	AIRS_EST_RAW = 0,     /* UNCOMPRESSED: 16 bits a sample */
+	AIRS_EST_ZERO_P2 = 1, /* GOLOMB_ZERO, g = 2^k: k + 1 + min((m + 1) >> k, 16) */
+	AIRS_EST_ZERO = 2,    /* GOLOMB_ZERO, any other g */
+	AIRS_EST_MULTI = 3    /* GOLOMB_MULTI */
+};
+struct airs_est_cand {
+	uint32_t kind;    /* enum airs_est_kind */
+	uint32_t pre;     /* enum cmp_preprocessing */
+	uint32_t k;       /* floor(log2 g) */
+	uint32_t cutoff;  /* 2^(k+1) - g */
+	uint32_t outlier; /* as cmp_coder_resolve leaves it */
+	uint32_t g;
+	uint32_t rcp;     /* airs_rcp_u32(g, 65537); not used when g is a power of two (shift) */
+	uint32_t hdr;     /* header bytes of a frame of this candidate: 16 or 22 */
+};
+struct airs_estimate {
+	const void *src;
+	uint64_t src_stride;
+	uint32_t sample_bytes, n, num_frames;
+	const uint16_t *model;
+	uint64_t model_stride;
+	const struct airs_est_cand *cand; /* host */
+	uint32_t num_cand;
+	uint64_t *bits;
+	uint32_t *best;
+};
+uint32_t airs_dev_estimate(struct airs_dev_engine *e, const struct airs_estimate *q);
+
+/* Host-side counters of the process, counted where the kernels are launched:
+ * sizing launches (one per group of candidates and chunk of frames), finishing
+ * launches (one per chunk), IWT transforms (one per chunk with an IWT
+ * candidate).  Copies the first min(n, AIRS_EST_STAT_COUNT) counters to out and
+ * returns AIRS_EST_STAT_COUNT.  For tests; nothing in the library reads them. */
+enum airs_est_stat {
+	AIRS_EST_STAT_SIZE = 0,
+	AIRS_EST_STAT_FINISH = 1,
+	AIRS_EST_STAT_IWT = 2,
+	AIRS_EST_STAT_COUNT = 3
+};
+uint32_t airs_dev_estimate_stats(uint64_t *out, uint32_t n);
 
 /* plain memory helpers on the engine stream */
 void *airs_dev_malloc(size_t bytes);

@@ -1,6 +1,6 @@
 /* cmp_engine.h -- the opaque cmp_gpu_engine of include/cmp_gpu.h (private to
  * the library's host code: cmp_host.c, cmp_gather.c, cmp_decode_seq.c,
- * cmp_decode_stream.c, cmp_decode_image.c, cmp_encode_image.c) */
+ * cmp_decode_stream.c, cmp_decode_image.c, cmp_encode_image.c, cmp_estimate.c) */
 #ifndef CMP_ENGINE_H
 #define CMP_ENGINE_H
 

@@ -1664,6 +1664,14 @@ static uint32_t run_iwt(struct airs_dev_engine *e, const struct airs_launch *L)
 	return 0;
 }
 
+extern "C" uint32_t airs_dev_iwt(struct airs_dev_engine *e, const struct airs_launch *L)
+{
+	if (!e || !L || L->n == 0 || L->num_frames == 0 || (!L->model && !L->model_ptrs) ||
+	    (L->sample_bytes != 2 && L->sample_bytes != 4))
+		return ERRV(E_GENERIC);
+	return run_iwt(e, L);
+}
+
 static uint32_t select_rice(struct airs_dev_engine *e, const void *src, uint64_t src_stride, uint32_t div,
 			    const uint64_t *ptrs, uint32_t sample_bytes, uint32_t n, uint32_t num_frames,
 			    const uint32_t *flist, uint32_t fadd, uint32_t fmul, uint32_t preprocessing, uint32_t *out_g);

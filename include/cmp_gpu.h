@@ -463,6 +463,93 @@ uint32_t cmp_gpu_decode_stream(struct cmp_gpu_engine *engine, const void *src, u
 			       uint16_t *dst, uint32_t *status);
 
 /*
+ * Size the frames of a batch under many parameter sets in one call, without
+ * coding them: which cmp_params should this data be compressed with?
+ *
+ * bits[f * num_candidates + c] (device) receives the exact number of payload
+ * bits that cmp_compress_<type> writes for frame f in a pass with candidate
+ * c's parameters, between the header and the flush: the sum over the frame's
+ * samples of the codeword length of cmp_encoder_encode_s16
+ * (lib/compress/encoder.c:327-378), the outlier resolved as for a frame
+ * (encoder.c:185-224).  CMP_PREPROCESS_NONE sizes the samples, DIFF
+ * x[i] - x[i-1] with x[0] as it is, IWT the frame's IWT coefficients, MODEL
+ * (int16)(x[i] - model[i]) with the model the caller passes.  The model is read
+ * and never updated: an estimate has no context and no sequence, and
+ * model_rate does not influence a size.  CMP_ENCODER_UNCOMPRESSED gives
+ * 16 * samples under every preprocessing.  For CMP_GPU_I16_IN_I32 only the low
+ * halves count, as everywhere else.  The values are integers: they do not
+ * depend on how the work is cut up or on run-to-run order.
+ *
+ * best[f] (device, optional) receives the index c that minimises
+ * 8 * H(c) + bits[f][c], ties to the lowest index, with H(c) the header of a
+ * frame coded with c: 16 bytes for NONE + UNCOMPRESSED and 22 otherwise.  With
+ * the sixteen candidates GOLOMB_ZERO g = 2^k listed in k order this is the
+ * CMP_GPU_AUTO_RICE rule.
+ *
+ * cmp_gpu_estimate_frame_size (host only, no device) turns a bit count into
+ * the size of the frame: H(c) + (bits + 7) / 8 + (checksum_enabled ? 4 : 0), or
+ * CMP_ERR_HDR_CMP_SIZE_TOO_LARGE when that exceeds CMP_HDR_MAX_COMPRESSED_SIZE;
+ * CMP_ERR_GENERIC for a NULL c, and for encoder arguments the encoder's own
+ * checks refuse the error those checks return.
+ *
+ * cmp_gpu_estimate returns CMP_ERR_NO_ERROR or a call-level refusal, before
+ * anything reaches the device, checked in this order:
+ *    1. NULL engine, batch, candidates or bits: CMP_ERR_GENERIC
+ *    2. num_frames 0 or above CMP_GPU_ESTIMATE_MAX_FRAMES: CMP_ERR_GENERIC
+ *    3. num_candidates 0 or above CMP_GPU_ESTIMATE_MAX_CANDIDATES: CMP_ERR_GENERIC
+ *    4. non-zero flags, an unknown type, bits not 8-byte aligned or best not
+ *       4-byte aligned: CMP_ERR_GENERIC
+ *    5. NULL src: CMP_ERR_SRC_NULL
+ *    6. src not aligned to the sample size: CMP_ERR_GENERIC
+ *    7. src_size 0 or not a multiple of the sample size: CMP_ERR_SRC_SIZE_WRONG
+ *    8. a packed size (2 bytes per sample) above CMP_HDR_MAX_ORIGINAL_SIZE:
+ *       CMP_ERR_HDR_ORIGINAL_TOO_LARGE
+ *    9. with more than one frame, a src_stride below src_size or not a multiple
+ *       of the sample size: CMP_ERR_GENERIC
+ *   10. per candidate, in index order: a preprocessing outside the four
+ *       CMP_ERR_PARAMS_INVALID; the error the encoder's own checks return; a
+ *       MODEL candidate with a NULL model, an odd model or model_stride, or
+ *       with more than one frame a model_stride below twice the samples:
+ *       CMP_ERR_PARAMS_INVALID.
+ *
+ * Asynchronous on the engine's stream: the call does not synchronise with the
+ * host, apart from engine scratch that has to grow; bits and best are valid
+ * after cmp_gpu_synchronize.  Nothing outside bits[0 .. num_frames *
+ * num_candidates) and best[0 .. num_frames) is written, and no byte outside
+ * the 16-byte aligned hull of the batch's samples (and models) is read.
+ * Build-defined extension.
+ */
+struct cmp_gpu_candidate {            /* one pass's parameters, as in cmp_params */
+	enum cmp_preprocessing preprocessing;   /* NONE, DIFF, IWT or MODEL */
+	enum cmp_encoder_type encoder_type;
+	uint32_t encoder_param;
+	uint32_t encoder_outlier;
+};
+#define CMP_GPU_ESTIMATE_MAX_CANDIDATES 64u
+#define CMP_GPU_ESTIMATE_MAX_FRAMES 1048576u
+
+struct cmp_gpu_estimate_batch {
+	enum cmp_gpu_sample_type type;
+	const void *src;          /* device; frame f at src + f*src_stride, 2-/4-byte aligned (16 is fastest) */
+	uint64_t src_stride;      /* bytes, multiple of the sample size, >= src_size when num_frames > 1 */
+	uint32_t src_size;        /* bytes per frame, as cmp_compress_*'s src_size */
+	uint32_t num_frames;
+	const uint16_t *model;    /* device or NULL: frame f's model (16-bit samples, as a work buffer holds
+				   * them) at model + f*model_stride bytes; needed by MODEL candidates only */
+	uint64_t model_stride;    /* bytes, even; >= 2 * samples when num_frames > 1 */
+	const struct cmp_gpu_candidate *candidates; /* HOST, read during the call only */
+	uint32_t num_candidates;
+	uint64_t *bits;           /* DEVICE [num_frames * num_candidates], 8-byte aligned:
+				   * bits[f*num_candidates + c] */
+	uint32_t *best;           /* DEVICE [num_frames], 4-byte aligned, or NULL */
+	uint32_t flags;           /* 0 */
+};
+uint32_t cmp_gpu_estimate(struct cmp_gpu_engine *engine, const struct cmp_gpu_estimate_batch *batch);
+
+/* host only, no device */
+uint32_t cmp_gpu_estimate_frame_size(const struct cmp_gpu_candidate *c, uint64_t bits, int checksum_enabled);
+
+/*
  * Pack the frames of a strided batch output (frame f at frames + f*frame_stride,
  * sizes[f] bytes, as cmp_gpu_compress leaves them) back to back into out: frame
  * f at out + offsets[f], offsets 8-byte aligned, offsets[num_frames] = the
