@@ -4,7 +4,7 @@
  * unequal sizes, compressed as one context into a packed .air image.  The
  * call-level validation returns before anything touches the device.  The
  * table is cut into runs of equal frames (cmp_image_plan.c); every run goes
- * through the batch path of cmp_gpu_compress (cmp_batch_compress, cmp_host.c)
+ * through the batch path of cmp_gpu_compress (cmp_batch_compress, cmp_batch.c)
  * between the copies of encode_image.hip: the ingest into aligned native rows
  * (skipped when the samples can be read where they are), then the offset scan
  * and the emit of the frame rows into the image.
@@ -133,7 +133,7 @@ uint32_t cmp_gpu_compress_image(struct cmp_gpu_engine *engine, struct cmp_contex
 		return ERRV(GENERIC);
 	d_off = (uint64_t *)(tables + 8u);
 	/* Straight from the caller's pageable table, as the batch path uploads its
-	 * identifiers (cmp_host.c): the runtime has staged a pageable source when
+	 * identifiers (cmp_batch.c): the runtime has staged a pageable source when
 	 * the copy call returns.  The engine's page-locked scratch is no place for
 	 * it: this call does not wait, and the next call on the engine may rewrite
 	 * that scratch while the copy is still queued. */

@@ -1,5 +1,5 @@
 /* cmp_engine.h -- the opaque cmp_gpu_engine of include/cmp_gpu.h (private to
- * the library's host code: cmp_host.c, cmp_gather.c, cmp_decode_seq.c,
+ * the library's host code: cmp_host.c, cmp_batch.c, cmp_gather.c, cmp_decode_seq.c,
  * cmp_decode_stream.c, cmp_decode_image.c, cmp_encode_image.c, cmp_estimate.c) */
 #ifndef CMP_ENGINE_H
 #define CMP_ENGINE_H
@@ -18,7 +18,7 @@ struct cmp_gpu_engine {
  * carries. */
 uint32_t cmp_coder_resolve(uint32_t type, uint32_t g, uint32_t outlier, uint32_t *resolved);
 
-/* The batch path behind cmp_gpu_compress (cmp_host.c), with its validation:
+/* The batch path behind cmp_gpu_compress (cmp_batch.c), with its validation:
  * cmp_gpu_compress_image runs every run of equal frames through it
  * (cmp_encode_image.c). */
 uint32_t cmp_batch_compress(struct cmp_gpu_engine *eng, struct cmp_context *ctx, uint32_t num_ctx, uint32_t fpc,

@@ -1,6 +1,6 @@
 /*
  * dev_stub.c -- TEST ONLY.  A host-memory stand-in for the HIP device layer
- * (airs_dev.h), so that the C host library (cmp_host.c: parameter checks,
+ * (airs_dev.h), so that the C host library (cmp_host.c, cmp_batch.c: parameter checks,
  * the context state machine, the batch planner and its step-by-step
  * fallback path) and the CLI parser can run under AddressSanitizer and
  * UndefinedBehaviorSanitizer on a machine without a GPU (SURVEY.md section 5,
@@ -42,6 +42,29 @@ uint64_t *airs_dev_coll(struct airs_dev_engine *e)
 {
 	return e ? e->coll : NULL;
 }
+
+/* Two 64-bit FNV-1a digests of what the host code asks of the device layer on
+ * this thread, folded field by field in call order (never over a struct's
+ * bytes, and never an address: a pointer enters as "is it NULL").  The launch
+ * digest covers what every launch-like call is handed and what the device
+ * would resolve per frame from it; the traffic digest covers scratch
+ * requests, copies and synchronisations.  host_fuzz.c prints both. */
+#define FNV_INIT 0xCBF29CE484222325ull
+__thread uint64_t stub_launch_digest = FNV_INIT;
+__thread uint64_t stub_traffic_digest = FNV_INIT;
+
+static void fnv(uint64_t *d, uint64_t v)
+{
+	for (int i = 0; i < 8; i++, v >>= 8)
+		*d = (*d ^ (v & 0xFFu)) * 0x100000001B3ull;
+}
+
+#define LD(v) fnv(&stub_launch_digest, (uint64_t)(v))
+#define LDP(p) fnv(&stub_launch_digest, (p) != NULL)
+#define TD(v) fnv(&stub_traffic_digest, (uint64_t)(v))
+enum { TAG_ENCODE = 1, TAG_WALK, TAG_WALK_SUPPORTED, TAG_FB_STEP, TAG_FB_COPY, TAG_CHECKSUM, TAG_SELECT_RICE,
+       TAG_PATCH_IDS, TAG_COMMIT_BEGIN, TAG_COMMIT_WAIT, TAG_COMMIT_RELEASE,
+       TAG_SCRATCH, TAG_HOST_SCRATCH, TAG_H2D, TAG_D2H, TAG_MEMSET, TAG_D2D_ROWS, TAG_SYNC };
 
 static uint64_t mix(uint64_t z)
 {
@@ -99,6 +122,7 @@ void *airs_dev_engine_stream(struct airs_dev_engine *e)
 
 void *airs_dev_scratch(struct airs_dev_engine *e, int slot, size_t bytes)
 {
+	TD(TAG_SCRATCH), TD(slot), TD(bytes);
 	if (!e || slot < 0 || slot >= AIRS_NSLOT || slot == stub_scratch_fail_slot)
 		return NULL;
 	if (bytes > e->cap[slot]) {
@@ -111,6 +135,7 @@ void *airs_dev_scratch(struct airs_dev_engine *e, int slot, size_t bytes)
 
 void *airs_dev_host_scratch(struct airs_dev_engine *e, size_t bytes)
 {
+	TD(TAG_HOST_SCRATCH), TD(bytes);
 	if (!e)
 		return NULL;
 	if (bytes > e->pinned_cap) {
@@ -121,14 +146,63 @@ void *airs_dev_host_scratch(struct airs_dev_engine *e, size_t bytes)
 	return e->pinned;
 }
 
+/* the model of launch frame j (batch frame f), whichever form was passed */
+static uint8_t *launch_model(const struct airs_launch *L, uint32_t j, uint32_t f)
+{
+	if (L->model_ptrs)
+		return (uint8_t *)(uintptr_t)L->model_ptrs[j];
+	return (uint8_t *)L->model + (uint64_t)(f / (L->model_div ? L->model_div : 1u)) * L->model_stride;
+}
+
+/* A model's place without its address: inside the engine's scratch (the
+ * coefficients of batch_iwt) the slot and the offset in it, otherwise the byte
+ * distance from the first such model of the launch (*base). */
+static void fold_model(const struct airs_dev_engine *e, const uint8_t *m, const uint8_t **base)
+{
+	for (int i = 0; i < AIRS_NSLOT; i++)
+		if (e->scratch[i] && m >= (const uint8_t *)e->scratch[i] && m < (const uint8_t *)e->scratch[i] + e->cap[i]) {
+			LD(1), LD(i), LD(m - (const uint8_t *)e->scratch[i]);
+			return;
+		}
+	if (!*base)
+		*base = m;
+	LD(0), LD(m - *base);
+}
+
+static void fold_launch(const struct airs_launch *L)
+{
+	LD(TAG_ENCODE);
+	LDP(L->src), LD(L->src_stride), LD(L->sample_bytes), LD(L->is_unsigned), LD(L->n), LD(L->num_frames);
+	LDP(L->frame_list), LD(L->frame_add), LD(L->frame_mul);
+	LDP(L->dst), LD(L->dst_stride), LD(L->cap);
+	LD(L->preprocessing), LD(L->encoder_type), LD(L->encoder_param), LD(L->outlier_param);
+	LDP(L->frame_g), LD(L->auto_rice), LDP(L->frame_g_scratch);
+	LDP(L->model), LD(L->model_stride), LD(L->model_div), LDP(L->model_ptrs), LD(L->model_ptrs_al16);
+	LD(L->model_mode), LD(L->model_rate), LD(L->fail_bit);
+	LDP(L->seqs), LD(L->id_base), LD(L->id_step), LDP(L->ids), LD(L->seq);
+	LD(L->checksum_enabled), LDP(L->checksums), LDP(L->status), LDP(L->needed);
+}
+
 uint32_t airs_dev_encode(struct airs_dev_engine *e, const struct airs_launch *L)
 {
+	const uint8_t *model0 = NULL;
+
+	if (L)
+		fold_launch(L);
 	if (!e || !L || !L->n || !L->num_frames || !L->status)
 		return ERRV(1u);
 	for (uint32_t j = 0; j < L->num_frames; j++) {
 		const uint32_t f = L->frame_list ? L->frame_list[j] : L->frame_add + j * L->frame_mul;
 		if (f == 0xFFFFFFFFu) /* AIRS_NO_FRAME: a hole in a device-planned list */
 			continue;
+		/* what the device resolves for this frame */
+		LD(f), LD(L->ids ? L->ids[j] : L->id_base + j * L->id_step);
+		if (L->seqs)
+			LD(L->seqs[f]);
+		if (L->model || L->model_ptrs)
+			fold_model(e, launch_model(L, j, f), &model0);
+		if (L->checksum_enabled && L->checksums)
+			LD(L->checksums[f]);
 		const uint64_t h = mix(e->salt++ ^ ((uint64_t)f << 32) ^ L->n);
 		/* every input byte the kernel would read is read here too */
 		const uint8_t *src = (const uint8_t *)L->src + (uint64_t)f * L->src_stride;
@@ -137,9 +211,7 @@ uint32_t airs_dev_encode(struct airs_dev_engine *e, const struct airs_launch *L)
 		uint32_t size = 16u + (uint32_t)(h % (3ull * L->n + 8u));
 		uint8_t *dst = (uint8_t *)L->dst + (uint64_t)f * L->dst_stride;
 		if (L->model_mode != AIRS_MODEL_NONE) {
-			uint8_t *m = L->model_ptrs ? (uint8_t *)(uintptr_t)L->model_ptrs[j]
-						   : (uint8_t *)L->model + (uint64_t)(f / (L->model_div ? L->model_div : 1u)) *
-									     L->model_stride;
+			uint8_t *m = launch_model(L, j, f);
 			m[0] ^= 1u; /* touch both ends of the model */
 			m[2u * L->n - 1u] ^= 1u;
 		}
@@ -173,7 +245,20 @@ uint32_t airs_dev_encode(struct airs_dev_engine *e, const struct airs_launch *L)
 
 /* the walk needs n % 4096 == 0 and 16-byte aligned inputs; the stub checks
  * the same so that the host's applicability test is exercised as written */
-int airs_dev_walk_supported(const struct airs_walk *w)
+static void fold_walk(uint32_t tag, const struct airs_walk *w)
+{
+	LD(tag);
+	LDP(w->src), LD(w->src_stride), LD(w->sample_bytes), LD(w->is_unsigned), LD(w->n), LD(w->num_ctx), LD(w->fpc);
+	LDP(w->dst), LD(w->dst_stride), LD(w->cap);
+	LDP(w->model), LD(w->model_stride), LDP(w->model_ptrs);
+	LD(w->pre_p), LD(w->enc_p), LD(w->g_p), LD(w->outl_p), LD(w->enc_s), LD(w->g_s), LD(w->outl_s);
+	LD(w->model_rate), LD(w->iters), LD(w->seq0), LDP(w->seq0s);
+	LD(w->id_base), LD(w->id_cstep), LD(w->id_astep), LDP(w->ids);
+	LD(w->checksum_enabled), LDP(w->checksums), LDP(w->status);
+	LD(w->fb), LD(w->raw_size), LDP(w->draws), LDP(w->seq_out);
+}
+
+static int walk_ok(const struct airs_walk *w)
 {
 	if (!w || !w->n || w->n % 4096u || !w->num_ctx || !w->fpc || (w->sample_bytes != 2 && w->sample_bytes != 4))
 		return 0;
@@ -185,11 +270,25 @@ int airs_dev_walk_supported(const struct airs_walk *w)
 	return w->model_ptrs || !(((uintptr_t)w->model & 15u) || (w->model_stride & 15u));
 }
 
+int airs_dev_walk_supported(const struct airs_walk *w)
+{
+	const int ok = walk_ok(w);
+
+	if (w)
+		fold_walk(TAG_WALK_SUPPORTED, w);
+	LD(ok);
+	return ok;
+}
+
 unsigned long stub_walk_calls;
 
 uint32_t airs_dev_walk(struct airs_dev_engine *e, struct airs_walk *w)
 {
-	if (!e || !airs_dev_walk_supported(w) || !w->status)
+	const uint8_t *model0 = NULL;
+
+	if (w)
+		fold_walk(TAG_WALK, w);
+	if (!e || !walk_ok(w) || !w->status)
 		return ERRV(10u);
 	stub_walk_calls++;
 	for (uint32_t c = 0; c < w->num_ctx; c++) {
@@ -207,10 +306,13 @@ uint32_t airs_dev_walk(struct airs_dev_engine *e, struct airs_walk *w)
 			(void)sink;
 			uint32_t size = 16u + (uint32_t)(h % (3ull * w->n + 8u));
 			uint8_t *dst = (uint8_t *)w->dst + (uint64_t)f * w->dst_stride;
-			if (w->ids)
-				(void)w->ids[f];
+			/* what the device resolves for this frame */
+			LD(f), LD(w->ids ? w->ids[f] : w->id_base + c * w->id_cstep + a * w->id_astep);
+			if (w->seq0s)
+				LD(w->seq0s[c]);
+			fold_model(e, m, &model0);
 			if (w->checksum_enabled && w->checksums)
-				(void)w->checksums[f];
+				LD(w->checksums[f]);
 			if (size > w->cap) {
 				/* the segment walk reports a frame that did not fit (the
 				 * host runs its context again); with fb the walk resolves
@@ -271,10 +373,30 @@ uint32_t airs_dev_pack_frames(struct airs_dev_engine *e, const void *src, uint64
 }
 
 /* the per-context state machine of fb_step_kernel (encode.hip), on the host */
+static void fold_fb(uint32_t tag, const struct airs_fb_step *a)
+{
+	LD(tag);
+	LDP(a->state), LD(a->num_ctx), LD(a->fpc), LD(a->prev), LD(a->cur), LD(a->packed), LD(a->iters);
+	LD(a->model_needed), LD(a->fb_eligible), LD(a->raw_size);
+	LD(a->err_floor), LD(a->err_small), LD(a->err_mismatch), LD(a->err_too_large);
+	LDP(a->flist_p), LDP(a->flist_s), LDP(a->seqs), LDP(a->draws), LDP(a->kind), LDP(a->fb), LDP(a->status);
+	LDP(a->src), LD(a->src_stride), LD(a->sample_bytes), LD(a->n), LDP(a->dst), LD(a->dst_stride);
+	LDP(a->checksums), LD(a->checksum), LDP(a->model), LD(a->model_stride), LDP(a->model_ptrs);
+}
+
+static uint8_t *fb_model(const struct airs_fb_step *a, uint32_t c)
+{
+	return a->model_ptrs ? (uint8_t *)(uintptr_t)a->model_ptrs[c] : (uint8_t *)a->model + (uint64_t)c * a->model_stride;
+}
+
 uint32_t airs_dev_fb_step(struct airs_dev_engine *e, const struct airs_fb_step *a)
 {
+	if (a)
+		fold_fb(TAG_FB_STEP, a);
 	if (!e || !a || !a->num_ctx)
 		return ERRV(1u);
+	for (uint32_t c = 0; c < a->num_ctx; c++) /* the states the step starts from */
+		LD(a->state[2u * c]), LD(a->state[2u * c + 1u]);
 	for (uint32_t c = 0; c < a->num_ctx; c++) {
 		uint32_t seq = a->state[2u * c], msize = a->state[2u * c + 1u];
 		if (a->prev >= 0) {
@@ -325,6 +447,10 @@ uint32_t airs_dev_fb_step(struct airs_dev_engine *e, const struct airs_fb_step *
 /* fb_copy_kernel: raw frames of the previous step's fallbacks */
 uint32_t airs_dev_fb_copy(struct airs_dev_engine *e, const struct airs_fb_step *a)
 {
+	const uint8_t *model0 = NULL;
+
+	if (a)
+		fold_fb(TAG_FB_COPY, a);
 	if (!e || !a || !a->num_ctx || a->prev < 0 || !a->n)
 		return ERRV(1u);
 	for (uint32_t c = 0; c < a->num_ctx; c++) {
@@ -334,9 +460,13 @@ uint32_t airs_dev_fb_copy(struct airs_dev_engine *e, const struct airs_fb_step *
 		const uint8_t *fs = (const uint8_t *)a->src + (uint64_t)f * a->src_stride;
 		uint8_t *fd = (uint8_t *)a->dst + (uint64_t)f * a->dst_stride;
 		uint16_t *fm = NULL;
-		if (a->model_needed)
-			fm = (uint16_t *)(a->model_ptrs ? (uint8_t *)(uintptr_t)a->model_ptrs[c]
-							: (uint8_t *)a->model + (uint64_t)c * a->model_stride);
+		LD(f);
+		if (a->model_needed) {
+			fm = (uint16_t *)fb_model(a, c);
+			fold_model(e, (const uint8_t *)fm, &model0);
+		}
+		if (a->checksum)
+			LD(a->checksums[f]);
 		memset(fd, 0, 16);
 		for (uint32_t i = 0; i < a->n; i++) {
 			const uint16_t x = a->sample_bytes == 2 ? ((const uint16_t *)fs)[i]
@@ -355,11 +485,13 @@ uint32_t airs_dev_fb_copy(struct airs_dev_engine *e, const struct airs_fb_step *
 uint32_t airs_dev_checksum(struct airs_dev_engine *e, const void *src, uint64_t src_stride, uint32_t sample_bytes,
 			   uint32_t n, uint32_t num_frames, const uint32_t *frame_list, uint32_t *out)
 {
+	LD(TAG_CHECKSUM), LDP(src), LD(src_stride), LD(sample_bytes), LD(n), LD(num_frames), LDP(frame_list), LDP(out);
 	if (!e || !n || !num_frames)
 		return ERRV(1u);
 	for (uint32_t j = 0; j < num_frames; j++) {
 		const uint32_t f = frame_list ? frame_list[j] : j;
 		const uint8_t *s = (const uint8_t *)src + (uint64_t)f * src_stride;
+		LD(f);
 		out[frame_list ? f : j] = s[0] + s[(uint64_t)n * sample_bytes - 1u];
 	}
 	return 0;
@@ -369,11 +501,15 @@ uint32_t airs_dev_select_rice(struct airs_dev_engine *e, const void *src, uint64
 			      uint32_t sample_bytes, uint32_t n, uint32_t num_frames, const uint32_t *frame_list,
 			      uint32_t frame_add, uint32_t frame_mul, uint32_t preprocessing, uint32_t *out_g)
 {
-	(void)e, (void)src, (void)src_stride, (void)sample_bytes, (void)n, (void)preprocessing;
+	(void)e;
+	LD(TAG_SELECT_RICE), LDP(src), LD(src_stride), LD(sample_bytes), LD(n), LD(num_frames), LDP(frame_list);
+	LD(frame_add), LD(frame_mul), LD(preprocessing), LDP(out_g);
 	for (uint32_t j = 0; j < num_frames; j++) {
 		const uint32_t f = frame_list ? frame_list[j] : frame_add + j * frame_mul;
-		if (f != 0xFFFFFFFFu)
+		if (f != 0xFFFFFFFFu) {
+			LD(f);
 			out_g[f] = 32u;
+		}
 	}
 	return 0;
 }
@@ -392,8 +528,10 @@ uint32_t airs_dev_patch_ids(struct airs_dev_engine *e, void *dst, uint64_t dst_s
 			    uint32_t frame_add, uint32_t frame_mul, const uint64_t *ids, const uint32_t *status)
 {
 	(void)e;
+	LD(TAG_PATCH_IDS), LDP(dst), LD(dst_stride), LD(num_frames), LD(frame_add), LD(frame_mul), LDP(ids), LDP(status);
 	for (uint32_t j = 0; j < num_frames; j++) {
 		const uint32_t f = frame_add + j * frame_mul;
+		LD(ids[j]);
 		if (status && status[f] > ERRV(128u))
 			continue;
 		for (int b = 0; b < 6; b++)
@@ -427,6 +565,7 @@ void airs_dev_free(void *p)
 uint32_t airs_dev_h2d(struct airs_dev_engine *e, void *dst, const void *src, size_t bytes)
 {
 	(void)e;
+	TD(TAG_H2D), TD(bytes);
 	if (stub_h2d_fail_at && --stub_h2d_fail_at == 0)
 		return ERRV(1u);
 	memcpy(dst, src, bytes);
@@ -436,6 +575,7 @@ uint32_t airs_dev_h2d(struct airs_dev_engine *e, void *dst, const void *src, siz
 uint32_t airs_dev_d2h(struct airs_dev_engine *e, void *dst, const void *src, size_t bytes)
 {
 	(void)e;
+	TD(TAG_D2H), TD(bytes);
 	memcpy(dst, src, bytes);
 	return 0;
 }
@@ -443,6 +583,7 @@ uint32_t airs_dev_d2h(struct airs_dev_engine *e, void *dst, const void *src, siz
 uint32_t airs_dev_sync(struct airs_dev_engine *e)
 {
 	(void)e;
+	TD(TAG_SYNC);
 	return 0;
 }
 
@@ -451,6 +592,7 @@ static uint8_t g_commit_flags[8192];
 uint32_t airs_dev_memset(struct airs_dev_engine *e, void *dst, int v, size_t bytes)
 {
 	(void)e;
+	TD(TAG_MEMSET), TD(v), TD(bytes);
 	memset(dst, v, bytes);
 	return 0;
 }
@@ -459,6 +601,7 @@ uint32_t airs_dev_d2d_rows(struct airs_dev_engine *e, void *dst, size_t dpitch, 
 			   size_t width, size_t rows)
 {
 	(void)e;
+	TD(TAG_D2D_ROWS), TD(dpitch), TD(spitch), TD(width), TD(rows);
 	for (size_t r = 0; r < rows; r++)
 		memmove((uint8_t *)dst + r * dpitch, (const uint8_t *)src + r * spitch, width);
 	return 0;
@@ -468,8 +611,7 @@ uint32_t airs_dev_commit_begin(struct airs_dev_engine *e, const uint32_t *status
 			       void *dst, uint64_t dst_stride, uint32_t *seq)
 {
 	(void)e;
-	(void)dst;
-	(void)dst_stride;
+	LD(TAG_COMMIT_BEGIN), LDP(status), LD(num_ctx), LD(fpc), LDP(dst), LD(dst_stride), LDP(seq);
 	for (uint32_t c = 0; c < num_ctx && c < sizeof(g_commit_flags); c++) {
 		uint32_t any = 0;
 		for (uint32_t a = 0; a < fpc; a++)
@@ -483,7 +625,7 @@ uint32_t airs_dev_commit_begin(struct airs_dev_engine *e, const uint32_t *status
 uint32_t airs_dev_commit_wait(struct airs_dev_engine *e, uint32_t seq, uint32_t num_ctx, uint8_t *flags)
 {
 	(void)e;
-	(void)seq;
+	LD(TAG_COMMIT_WAIT), LD(seq), LD(num_ctx), LDP(flags);
 	memcpy(flags, g_commit_flags, num_ctx < sizeof(g_commit_flags) ? num_ctx : sizeof(g_commit_flags));
 	return 0;
 }
@@ -491,9 +633,9 @@ uint32_t airs_dev_commit_wait(struct airs_dev_engine *e, uint32_t seq, uint32_t 
 int airs_dev_commit_release(struct airs_dev_engine *e, uint32_t seq, const uint64_t *ids, uint32_t total)
 {
 	(void)e;
-	(void)seq;
-	(void)ids;
-	(void)total;
+	LD(TAG_COMMIT_RELEASE), LD(seq), LD(total), LDP(ids);
+	for (uint32_t f = 0; ids && f < total; f++)
+		LD(ids[f]);
 	return 0; /* the caller patches */
 }
 

@@ -22,6 +22,10 @@
 static uint64_t g_rng;
 /* outcome counters: the run must reach the interesting paths */
 extern unsigned long stub_walk_calls; /* dev_stub.c */
+/* dev_stub.c: what the planner handed to the device layer (every launch-like
+ * call, field by field and frame by frame), and its scratch requests, copies
+ * and synchronisations in call order */
+extern __thread uint64_t stub_launch_digest, stub_traffic_digest;
 static uint32_t n_init_ok, n_frames_ok, n_frames_err, n_batch_ok, n_batch_frames_ok, n_batch_fallback_cap,
 	n_stream_ok;
 
@@ -422,5 +426,7 @@ int main(int argc, char **argv)
 	       "%u batches (%u frames ok, %u with fallback enabled), %u streams, %lu walks, digest %016llx\n",
 	       iters, n_init_ok, n_frames_ok, n_frames_err, n_batch_ok, n_batch_frames_ok, n_batch_fallback_cap,
 	       n_stream_ok, stub_walk_calls, (unsigned long long)g_digest);
+	printf("launch digest %016llx, traffic digest %016llx\n", (unsigned long long)stub_launch_digest,
+	       (unsigned long long)stub_traffic_digest);
 	return 0;
 }

@@ -178,7 +178,7 @@ def _clip_run(prod, eng, orc, kind, pre, k, frames, checksum, cap):
 def test_lookback_capacity_clipping_batch(prod, eng, orc, k, pre):
     """Clipping in a batch of 8 frames x 17 segments whose every other frame
     does not fit.  A capacity below the bound sends the batch through the
-    exact-mode path (cmp_host.c, cmp_gpu_compress); with one context per frame
+    exact-mode path (cmp_batch.c, cmp_gpu_compress); with one context per frame
     and equal parameters that is batch_device_exact, which launches the 8
     frames of an acquisition step together, through a frame list: ONE Rice
     launch with lbmode 1, asserted.  (One context with 8 frames would be 8

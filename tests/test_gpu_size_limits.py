@@ -19,7 +19,7 @@ test_size_cases.py) put frames on the limit and a byte or a bit either side:
   fb_step_kernel: v == err_small, raw_size > 0xFFFFFF
     (encode.hip)                                           test_fallback_routes[stepwise], test_fallback_24bit[stepwise]
   model_fail_bit = 64 (cap / 8) + 63 (cmp_host.c)          test_model_fail_bit (every route)
-  fb_eligible, walk eligibility from raw (cmp_host.c)      test_fallback_routes, test_fallback_24bit[flags0]
+  fb_eligible, walk eligibility from raw (cmp_batch.c)     test_fallback_routes, test_fallback_24bit[flags0]
   size > 0xFFFFFF, Rice kernel and encode_kernel           test_size_field_24bit
 
 Expectations always come from the oracle's call loop
@@ -250,7 +250,7 @@ def test_model_fail_bit(prod, eng, orc, orc_ext, route, res):
     model, the sample that ends on the next bit is the first that keeps the
     old one, and so is an escape of which only the second piece crosses.  The
     work buffer is compared byte for byte, and the next frame, which is coded
-    against it.  Without the fallback no walk takes such a batch (cmp_host.c
+    against it.  Without the fallback no walk takes such a batch (cmp_batch.c
     walk_prepare: exact mode needs the fallback): flags 0 is encode_kernel
     with a model under the device state machine, asserted."""
     case = lc.failbit(orc, ("u16", "i16_in_i32", "i16")[res % 3], 12288, res, res & 1)

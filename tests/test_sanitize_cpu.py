@@ -1,6 +1,6 @@
 """SURVEY.md section 5, sanitizer row: the host C code of libairscmp.so
-(cmp_host.c: argument checks, the context state machine, the batch planner
-with its step-by-step fallback path) and the CLI --params parser built with
+(cmp_host.c, cmp_batch.c: argument checks, the context state machine, the batch
+planner with its step-by-step fallback path) and the CLI --params parser built with
 AddressSanitizer + UndefinedBehaviorSanitizer (tests/sanitize/Makefile) and
 driven by tests/sanitize/host_fuzz.c over pseudo-random valid and invalid
 inputs.  The device layer is a host-memory stub (tests/sanitize/dev_stub.c),
