@@ -342,6 +342,8 @@ static int dev_open(struct dev *d)
 		d->eng = NULL;
 		return -1;
 	}
+	/* files of unequal sizes share one encode launch (no result depends on it) */
+	(void)cmp_gpu_engine_set_option(d->eng, CMP_GPU_OPT_IMAGE_RAGGED, 1);
 	return 0;
 }
 

@@ -39,6 +39,8 @@ GPU_AUTO_RICE = 0x1
 GPU_HOST_STEPPED = 0x2
 GPU_STEPWISE = 0x4
 GPU_REPORT_DRAWS = 0x8
+# cmp_gpu_engine_set_option: frames of unequal sizes of cmp_gpu_compress_image in one launch
+GPU_OPT_IMAGE_RAGGED = 5
 
 
 def err_value(name: str) -> int:

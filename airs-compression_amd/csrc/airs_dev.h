@@ -218,7 +218,8 @@ uint32_t airs_dev_synth(struct airs_dev_engine *e, void *dst, uint32_t sample_by
 		       * placement, checksum products, decoder parse arrays, decoder frame info, IWT heads) */
 #define AIRS_SLOT_GATHER 11 /* slots 11..13: cmp_gpu_gather (cmp_gather.c); 0..10 cmp_host.c */
 #define AIRS_SLOT_IMAGE 14 /* slots 14..16: airs_dev_decode_image (tables, staging rows, model) */
-#define AIRS_SLOT_ENCIMG 17 /* slots 17..19: cmp_gpu_compress_image (tables, sample rows, frame rows) */
+#define AIRS_SLOT_ENCIMG 17 /* slots 17..19: cmp_gpu_compress_image (tables, with those of its ragged
+			     * pieces behind them; sample rows; frame rows) */
 #define AIRS_SLOT_ESTIMATE 20 /* slots 20..21: airs_dev_estimate (slice partials, IWT coefficients) */
 void *airs_dev_scratch(struct airs_dev_engine *e, int slot, size_t bytes);
 /* engine-owned device words for the gather's status exchanges (cmp_gather.c),
@@ -370,8 +371,64 @@ struct airs_encode_image {
 	uint64_t out_capacity;
 	uint32_t first_run;
 	uint32_t force;
+	/* a ragged piece (frames of unequal sizes, all optional, device [count]):
+	 * the ingest writes row_len[j] bytes of frame j to rows + row_off[j] (16-byte
+	 * aligned; 0 bytes: the frame is read where it lies, nothing is copied) and
+	 * frame_bytes is the largest row_len; the emit takes frame row j at
+	 * frows + frow_off[j] (8-byte aligned) and frow_cap is the largest capacity.
+	 * staged: the frames the ingest counts (those with row_len != 0). */
+	const uint64_t *row_off;
+	const uint32_t *row_len;
+	const uint64_t *frow_off;
+	uint32_t staged;
 };
 uint32_t airs_dev_encode_image(struct airs_dev_engine *e, const struct airs_encode_image *q);
+
+/* One ragged encode launch (enc_ragged.hip; cmp_gpu_compress_image with
+ * CMP_GPU_OPT_IMAGE_RAGGED, planned by cmp_image_plan.c): frames of different
+ * sizes, one pass (NONE or DIFF, any coder, no model, no checksum).  Block b
+ * of the launch encodes segment desc[b].seg of the frame desc[b] describes;
+ * the blocks of a frame stand in ascending segment order.  The frame arrays
+ * are indexed by desc[b].frame.  Granule slots desc[b].slot0 + seg lie below
+ * `slots`.  Everything is queued; nothing synchronises unless the engine's
+ * look-back granules have to grow. */
+struct airs_ragged_desc {
+	uint64_t src;    /* device address of the frame's first sample (a multiple of sample_bytes) */
+	uint32_t n;      /* samples of the frame, >= 1 */
+	uint32_t seg;    /* this block's segment of the frame */
+	uint32_t frame;  /* the frame's index in the frame arrays */
+	uint32_t slot0;  /* the frame's first look-back granule slot (frame-major) */
+	uint32_t rsv[2];
+};
+struct airs_ragged {
+	uint32_t sample_bytes;   /* 2 or 4 */
+	uint32_t frames;         /* frames the launch encodes (the counter) */
+	uint32_t blocks;
+	uint32_t slots;
+	const struct airs_ragged_desc *desc; /* device [blocks], 32-byte aligned */
+	void *dst;               /* frame j's row at dst + dst_off[j] */
+	const uint64_t *dst_off; /* device, multiples of 8 */
+	const uint32_t *caps;    /* device */
+	const uint64_t *ids;     /* device */
+	const uint8_t *seqs;     /* device */
+	uint32_t preprocessing, encoder_type, encoder_param, outlier_param;
+	uint32_t *status;        /* device: frame size or error value */
+};
+uint32_t airs_dev_encode_ragged(struct airs_dev_engine *e, const struct airs_ragged *q);
+/* samples per segment of the ragged kernel for samples of sample_bytes bytes */
+uint32_t airs_dev_ragged_segment(uint32_t sample_bytes);
+
+/* Host-side counters of the process, counted where the kernel is launched:
+ * ragged encode launches, the frames they encoded, their blocks.  Copies the
+ * first min(n, AIRS_RAGGED_STAT_COUNT) counters to out and returns
+ * AIRS_RAGGED_STAT_COUNT.  For tests; nothing in the library reads them. */
+enum airs_ragged_stat {
+	AIRS_RAGGED_STAT_LAUNCHES = 0,
+	AIRS_RAGGED_STAT_FRAMES = 1,
+	AIRS_RAGGED_STAT_BLOCKS = 2,
+	AIRS_RAGGED_STAT_COUNT = 3
+};
+uint32_t airs_dev_ragged_stats(uint64_t *out, uint32_t n);
 
 /* Host-side counters of the process, counted where the kernels are launched:
  * frames that went through the ingest copy (a run read where it lies adds

@@ -8,8 +8,15 @@
  * between the copies of encode_image.hip: the ingest into aligned native rows
  * (skipped when the samples can be read where they are), then the offset scan
  * and the emit of the frame rows into the image.
+ *
+ * With CMP_GPU_OPT_IMAGE_RAGGED and a context whose frames are independent
+ * the table is cut into pieces instead (cmp_image_piece_next): refused frames
+ * and large runs of equal frames go the same way as above, every other frame
+ * joins a ragged piece, which is one ingest, one encode launch per pass
+ * (enc_ragged.hip), one scan and one emit.
  */
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "cmp.h"
@@ -18,13 +25,18 @@
 #include "airs_dev.h"
 #include "cmp_engine.h"
 #include "cmp_image_plan.h"
+#include "cmp_pass.h"
 
-#define ERRV(name) ((uint32_t)0u - (uint32_t)CMP_ERR_##name)
 #define BATCH_FLAGS (CMP_GPU_AUTO_RICE | CMP_GPU_HOST_STEPPED | CMP_GPU_STEPWISE)
 
 static uint32_t up16(uint32_t v)
 {
 	return (v + 15u) & ~15u;
+}
+
+static uint32_t up8(uint32_t v)
+{
+	return (v + 7u) & ~7u;
 }
 
 /* what the loop's cmp_compress_* call answers for frames of fb bytes before it
@@ -42,41 +54,390 @@ static uint32_t frame_refusal(uint32_t fb, uint32_t sample_bytes, uint32_t *boun
 	return 0;
 }
 
+/* one call's state */
+struct image_job {
+	struct cmp_gpu_engine *engine;
+	struct airs_dev_engine *dev;
+	struct cmp_context *ctx;
+	const struct cmp_gpu_encode_image *img;
+	uint32_t sample_bytes, first_run;
+	uint32_t *bound;   /* host [num_frames], 0 for a refused frame: ragged calls only (else NULL) */
+	uint64_t keep;     /* the keep threshold of a ragged call */
+	uint32_t seg;      /* samples per segment of the ragged kernel */
+	/* engine scratch */
+	uint8_t *tables;   /* the sticky word, then d_off, then the ragged tables */
+	uint64_t *d_off;   /* the offsets of the frames in src */
+	uint8_t *rag;      /* the tables of one ragged piece (struct rag_layout) */
+	uint8_t *rows, *frows;
+};
+
 /* The batch path can read the run's samples where they are: native-endian, the
  * first frame aligned to the sample size, the offsets an arithmetic
  * progression whose step is at least the frame and a multiple of the sample
  * size. */
-static int run_direct(const struct cmp_gpu_encode_image *img, const struct cmp_image_run *r, uint32_t sample_bytes,
+static int run_direct(const struct cmp_gpu_encode_image *img, uint64_t first, uint32_t count, uint32_t sample_bytes,
 		      uint64_t *stride)
 {
-	const uint64_t *o = img->offsets + r->first;
-	const uint32_t fb = img->frame_bytes[r->first];
+	const uint64_t *o = img->offsets + first;
+	const uint32_t fb = img->frame_bytes[first];
 	uint32_t j;
 
 	if ((img->flags & CMP_GPU_IMG_SRC_BIG_ENDIAN) || ((uintptr_t)img->src + o[0]) % sample_bytes)
 		return 0;
 	*stride = fb;
-	if (r->count == 1)
+	if (count == 1)
 		return 1;
 	if (o[1] < o[0] || o[1] - o[0] < fb || (o[1] - o[0]) % sample_bytes)
 		return 0;
 	*stride = o[1] - o[0];
-	for (j = 2; j < r->count; j++)
+	for (j = 2; j < count; j++)
 		if (o[j] < o[j - 1] || o[j] - o[j - 1] != *stride)
 			return 0;
+	return 1;
+}
+
+/* a frame of a ragged piece is read where it lies: native-endian, at a
+ * multiple of the sample size (its neighbours do not matter) */
+static int frame_direct(const struct cmp_gpu_encode_image *img, uint64_t f, uint32_t sample_bytes)
+{
+	return !(img->flags & CMP_GPU_IMG_SRC_BIG_ENDIAN) && ((uintptr_t)img->src + img->offsets[f]) % sample_bytes == 0;
+}
+
+/* the next piece of the table: the runs of equal frames, or with the ragged
+ * option the pieces of cmp_image_piece_next */
+static void next_piece(const struct image_job *J, uint64_t f, struct cmp_image_piece *p)
+{
+	const struct cmp_gpu_encode_image *img = J->img;
+
+	if (J->bound) {
+		cmp_image_piece_next(img->frame_bytes, J->bound, img->num_frames, J->engine->image_chunk, J->keep, 0, f, p);
+	} else {
+		const uint32_t fb = img->frame_bytes[f];
+		struct cmp_image_run r;
+		uint32_t bound;
+		const uint32_t refused = frame_refusal(fb, J->sample_bytes, &bound);
+
+		cmp_image_run_next(img->frame_bytes, img->num_frames, J->engine->image_chunk, cmp_image_run_row(fb, bound),
+				   0, f, &r);
+		p->first = f;
+		p->count = r.count;
+		p->kind = refused ? CMP_IMAGE_PIECE_REFUSED : CMP_IMAGE_PIECE_RUN;
+	}
+}
+
+/* The device tables of one ragged piece of cnt frames and `blocks` blocks, as
+ * byte offsets into one region that a single copy uploads: the descriptors of
+ * both passes' launches, then the per-frame arrays. */
+struct rag_layout {
+	size_t desc, dst_off, ids, row_off, caps, row_len, seqs, total;
+};
+
+static void rag_layout(uint32_t cnt, uint64_t blocks, struct rag_layout *L)
+{
+	size_t at = 0;
+
+	L->desc = at;
+	at += (size_t)blocks * sizeof(struct airs_ragged_desc);
+	L->dst_off = at;
+	at += (size_t)cnt * 8u;
+	L->ids = at;
+	at += (size_t)cnt * 8u;
+	L->row_off = at;
+	at += (size_t)cnt * 8u;
+	L->caps = at;
+	at += (size_t)cnt * 4u;
+	L->row_len = at;
+	at += (size_t)cnt * 4u;
+	L->seqs = at;
+	at += cnt;
+	L->total = (at + 31u) & ~(size_t)31u;
+}
+
+static uint32_t frame_segs(const struct image_job *J, uint64_t f)
+{
+	const uint32_t n = J->img->frame_bytes[f] / J->sample_bytes;
+
+	return (n + J->seg - 1u) / J->seg;
+}
+
+/* the scan and the emit of one piece (refused: the scan alone) */
+static uint32_t piece_emit(struct image_job *J, uint64_t f, uint32_t count, uint32_t frow_cap, const uint64_t *frow_off,
+			   uint32_t refused)
+{
+	const struct cmp_gpu_encode_image *img = J->img;
+	struct airs_encode_image q;
+	uint32_t e;
+
+	memset(&q, 0, sizeof(q));
+	q.stage = AIRS_ENCIMG_EMIT;
+	q.count = count;
+	q.frows = J->frows;
+	q.frow_bytes = up8(frow_cap);
+	q.frow_cap = frow_cap;
+	q.frow_off = frow_off;
+	q.sizes = img->sizes + f;
+	q.out_offsets = img->out_offsets + f;
+	q.sticky = (uint32_t *)J->tables;
+	q.out = img->out;
+	q.out_capacity = img->out_capacity;
+	q.first_run = J->first_run;
+	q.force = refused;
+	e = airs_dev_encode_image(J->dev, &q);
+	J->first_run = 0;
+	return e;
+}
+
+/* one run of equal frames through the batch path */
+static uint32_t piece_run(struct image_job *J, uint64_t f, uint32_t count)
+{
+	const struct cmp_gpu_encode_image *img = J->img;
+	const uint32_t fb = img->frame_bytes[f];
+	uint32_t bound, e;
+	const uint32_t refused = frame_refusal(fb, J->sample_bytes, &bound);
+
+	if (!refused) {
+		struct cmp_gpu_batch b;
+		uint64_t stride = 0;
+
+		memset(&b, 0, sizeof(b));
+		b.type = img->type;
+		if (run_direct(img, f, count, J->sample_bytes, &stride)) {
+			b.src = (const uint8_t *)img->src + img->offsets[f];
+			b.src_stride = stride;
+		} else {
+			struct airs_encode_image q;
+
+			memset(&q, 0, sizeof(q));
+			q.stage = AIRS_ENCIMG_INGEST;
+			q.count = count;
+			q.src = img->src;
+			q.offsets = J->d_off + f;
+			q.frame_bytes = fb;
+			q.swap = (img->flags & CMP_GPU_IMG_SRC_BIG_ENDIAN) != 0;
+			q.rows = J->rows;
+			q.row_bytes = up16(fb);
+			e = airs_dev_encode_image(J->dev, &q);
+			if (e)
+				return e;
+			b.src = J->rows;
+			b.src_stride = q.row_bytes;
+		}
+		b.src_size = fb;
+		b.dst = J->frows;
+		b.dst_stride = up8(bound);
+		b.dst_capacity = bound;
+		b.sizes = img->sizes + f;
+		b.flags = img->batch_flags;
+		e = cmp_batch_compress(J->engine, J->ctx, 1, count, &b);
+		if (e)
+			return e;
+	}
+	return piece_emit(J, f, count, bound, NULL, refused);
+}
+
+/* One ragged piece: frames [first, first + cnt), none refused.  The context is
+ * replayed over them on the host as the batch path replays its frames
+ * (batch_replay, cmp_batch.c): every frame's pass, header sequence number and
+ * identifier, the draws in table order, the context's final fields.  The
+ * frames of a pass share one launch; their tables go up in one copy from
+ * pageable memory, which the runtime has staged when the copy call returns
+ * (see the offsets' upload in cmp_gpu_compress_image). */
+static uint32_t piece_ragged(struct image_job *J, uint64_t first, uint32_t cnt)
+{
+	const struct cmp_gpu_encode_image *img = J->img;
+	const struct cmp_context snap = *J->ctx;
+	const uint32_t sb = J->sample_bytes;
+	struct rag_layout L;
+	struct pass *pass = NULL;
+	struct cmp_image_block *blk = NULL;
+	struct airs_ragged_desc *desc;
+	uint32_t *segs = NULL, *slot0, *gsegs, *active, *caps, *row_len;
+	uint64_t *dst_off, *ids, *row_off, blocks = 0, done = 0, at, id;
+	uint8_t *hb = NULL, *seqs;
+	uint32_t j, g, e = ERRV(GENERIC), staged = 0, max_len = 0, max_cap = 0, slots = 0;
+	uint64_t gfirst[2] = {0, 0}, gblocks[2] = {0, 0};
+	uint32_t gframes[2] = {0, 0}, gmember[2] = {0, 0};
+
+	for (j = 0; j < cnt; j++)
+		blocks += frame_segs(J, first + j);
+	if (blocks > 0x7FFFFFFFu)
+		return ERRV(GENERIC);
+	rag_layout(cnt, blocks, &L);
+	hb = calloc(1, L.total);
+	pass = malloc((size_t)cnt * sizeof(*pass));
+	blk = malloc((size_t)(blocks ? blocks : 1u) * sizeof(*blk));
+	segs = malloc((size_t)cnt * 4u * sizeof(*segs));
+	if (!hb || !pass || !blk || !segs)
+		goto out;
+	slot0 = segs + cnt;
+	gsegs = slot0 + cnt;
+	active = gsegs + cnt;
+	desc = (struct airs_ragged_desc *)(hb + L.desc);
+	dst_off = (uint64_t *)(hb + L.dst_off);
+	ids = (uint64_t *)(hb + L.ids);
+	row_off = (uint64_t *)(hb + L.row_off);
+	caps = (uint32_t *)(hb + L.caps);
+	row_len = (uint32_t *)(hb + L.row_len);
+	seqs = hb + L.seqs;
+
+	/* the replay; the draws are made below, all of the piece's in table order */
+	id = snap.identifier;
+	for (j = 0; j < cnt; j++) {
+		const uint32_t fb = img->frame_bytes[first + j];
+		uint32_t drawn = 0, k;
+
+		if (is_err(engine_prologue(J->ctx, J->frows, J->bound[first + j], fb / sb, &pass[j], &drawn))) {
+			*J->ctx = snap; /* the call's eligibility check rules this out */
+			goto out;
+		}
+		J->ctx->sequence_number++;
+		for (k = 0; k < drawn; k++)
+			id = next_identifier();
+		ids[j] = id;
+		seqs[j] = pass[j].seq;
+	}
+	J->ctx->identifier = id;
+
+	/* the geometry: frame rows at 8-byte, sample rows at 16-byte aligned prefix offsets */
+	for (j = 0, at = 0; j < cnt; j++) {
+		const uint32_t b = J->bound[first + j];
+
+		dst_off[j] = at;
+		at += up8(b);
+		caps[j] = b;
+		max_cap = b > max_cap ? b : max_cap;
+		segs[j] = frame_segs(J, first + j);
+		slot0[j] = slots;
+		slots += segs[j];
+	}
+	for (j = 0, at = 0; j < cnt; j++) {
+		const uint32_t fb = img->frame_bytes[first + j];
+
+		row_off[j] = at;
+		if (frame_direct(img, first + j, sb))
+			continue;
+		row_len[j] = fb;
+		at += up16(fb);
+		staged++;
+		max_len = fb > max_len ? fb : max_len;
+	}
+	/* the launches: the primary pass's frames (sequence number 0), then the secondary's */
+	for (g = 0; g < 2; g++) {
+		uint64_t nb, i;
+
+		for (j = 0; j < cnt; j++) {
+			const int member = (pass[j].seq != 0) == (int)g;
+
+			gsegs[j] = member ? segs[j] : 0u;
+			if (member && !gframes[g]++)
+				gmember[g] = j;
+		}
+		if (!gframes[g])
+			continue;
+		nb = cmp_image_ragged_blocks(gsegs, cnt, active, blk + done);
+		for (i = 0; i < nb; i++) {
+			struct airs_ragged_desc *d = &desc[done + i];
+			const uint32_t fj = blk[done + i].frame;
+
+			d->src = row_len[fj] ? (uint64_t)(uintptr_t)J->rows + row_off[fj]
+					     : (uint64_t)(uintptr_t)img->src + img->offsets[first + fj];
+			d->n = img->frame_bytes[first + fj] / sb;
+			d->seg = blk[done + i].seg;
+			d->frame = fj;
+			d->slot0 = slot0[fj];
+		}
+		gfirst[g] = done;
+		gblocks[g] = nb;
+		done += nb;
+	}
+	if (airs_dev_h2d(J->dev, J->rag, hb, L.total))
+		goto out;
+	if (staged) {
+		struct airs_encode_image q;
+
+		memset(&q, 0, sizeof(q));
+		q.stage = AIRS_ENCIMG_INGEST;
+		q.count = cnt;
+		q.src = img->src;
+		q.offsets = J->d_off + first;
+		q.frame_bytes = max_len;
+		q.swap = (img->flags & CMP_GPU_IMG_SRC_BIG_ENDIAN) != 0;
+		q.rows = J->rows;
+		q.row_off = (const uint64_t *)(J->rag + L.row_off);
+		q.row_len = (const uint32_t *)(J->rag + L.row_len);
+		q.staged = staged;
+		e = airs_dev_encode_image(J->dev, &q);
+		if (e)
+			goto out;
+	}
+	for (g = 0; g < 2; g++) {
+		const struct pass *p = &pass[gmember[g]];
+		struct airs_ragged r;
+
+		if (!gframes[g])
+			continue;
+		memset(&r, 0, sizeof(r));
+		r.sample_bytes = sb;
+		r.frames = gframes[g];
+		r.blocks = (uint32_t)gblocks[g];
+		r.slots = slots;
+		r.desc = (const struct airs_ragged_desc *)(J->rag + L.desc) + gfirst[g];
+		r.dst = J->frows;
+		r.dst_off = (const uint64_t *)(J->rag + L.dst_off);
+		r.caps = (const uint32_t *)(J->rag + L.caps);
+		r.ids = (const uint64_t *)(J->rag + L.ids);
+		r.seqs = J->rag + L.seqs;
+		r.preprocessing = p->pre;
+		r.encoder_type = p->enc;
+		r.encoder_param = p->par;
+		r.outlier_param = p->outlier_param;
+		r.status = img->sizes + first;
+		e = airs_dev_encode_ragged(J->dev, &r);
+		if (e)
+			goto out;
+	}
+	e = piece_emit(J, first, cnt, max_cap, (const uint64_t *)(J->rag + L.dst_off), 0);
+out:
+	free(hb);
+	free(pass);
+	free(blk);
+	free(segs);
+	return e;
+}
+
+/* The ragged path applies: the option is on, the frames of the context are
+ * independent (no state in the work buffer), no frame can fall back, nothing
+ * needs the checksum's own two launches or the batch path's flags, and the
+ * context's passes are ones the prologue accepts (tried on a copy, with the
+ * draws only counted). */
+static int ragged_applies(const struct image_job *J)
+{
+	const struct cmp_params *P = &J->ctx->params;
+	struct cmp_context c = *J->ctx;
+	struct pass p;
+	uint32_t drawn = 0;
+	uint64_t dummy[4];
+
+	if (!J->engine->image_ragged || work_buf_state(P) || P->checksum_enabled || P->uncompressed_fallback_enabled ||
+	    J->img->batch_flags)
+		return 0;
+	c.sequence_number = 0;
+	if (is_err(engine_prologue(&c, dummy, HDR_MAX_SIZE, 1, &p, &drawn)))
+		return 0;
+	c.sequence_number = 1;
+	if (P->secondary_iterations && is_err(engine_prologue(&c, dummy, HDR_MAX_SIZE, 1, &p, &drawn)))
+		return 0;
 	return 1;
 }
 
 uint32_t cmp_gpu_compress_image(struct cmp_gpu_engine *engine, struct cmp_context *ctx,
 				const struct cmp_gpu_encode_image *img)
 {
-	struct cmp_image_run r;
-	struct airs_dev_engine *dev;
-	uint64_t f, N, stride = 0;
-	size_t rows_bytes = 0, frows_bytes = 0;
-	uint32_t sample_bytes, bound, e, staged = 0, first_run = 1;
-	uint8_t *tables, *rows = NULL, *frows;
-	uint64_t *d_off;
+	struct image_job J;
+	struct cmp_image_piece p;
+	uint64_t f, N;
+	size_t rows_bytes = 0, frows_bytes = 0, rag_bytes = 0, rag_at;
+	uint32_t sample_bytes, e = 0, staged = 0;
 
 	if (!engine || !ctx || !img || !img->offsets || !img->frame_bytes || !img->out_offsets || !img->sizes ||
 	    !img->num_frames)
@@ -103,98 +464,82 @@ uint32_t cmp_gpu_compress_image(struct cmp_gpu_engine *engine, struct cmp_contex
 	e = cmp_context_usable(ctx);
 	if (e)
 		return e;
-	dev = engine->dev;
 	sample_bytes = img->type == CMP_GPU_I16_IN_I32 ? 4u : 2u;
-
-	/* the rows of the largest run, allocated once: growing them between runs
-	 * would wait for the stream */
-	for (f = 0; f < N; f += r.count) {
-		const uint32_t fb = img->frame_bytes[f];
-		const uint32_t refused = frame_refusal(fb, sample_bytes, &bound);
-		size_t need;
-
-		cmp_image_run_next(img->frame_bytes, N, engine->image_chunk, cmp_image_run_row(fb, bound), 0, f, &r);
-		if (refused)
-			continue;
-		need = (size_t)r.count * ((bound + 7u) & ~7u);
-		frows_bytes = need > frows_bytes ? need : frows_bytes;
-		if (run_direct(img, &r, sample_bytes, &stride))
-			continue;
-		staged = 1;
-		need = (size_t)r.count * up16(fb);
-		rows_bytes = need > rows_bytes ? need : rows_bytes;
+	memset(&J, 0, sizeof(J));
+	J.engine = engine;
+	J.dev = engine->dev;
+	J.ctx = ctx;
+	J.img = img;
+	J.sample_bytes = sample_bytes;
+	J.first_run = 1;
+	if (ragged_applies(&J)) {
+		J.bound = malloc((size_t)N * sizeof(*J.bound));
+		if (!J.bound)
+			return ERRV(GENERIC);
+		for (f = 0; f < N; f++)
+			(void)frame_refusal(img->frame_bytes[f], sample_bytes, &J.bound[f]);
+		J.keep = engine->image_ragged == 1u ? CMP_IMAGE_RAGGED_KEEP : engine->image_ragged;
+		J.seg = airs_dev_ragged_segment(sample_bytes);
 	}
-	/* the sticky word, then the offsets of the frames in src */
-	tables = airs_dev_scratch(dev, AIRS_SLOT_ENCIMG, 8u + (staged ? (size_t)N * 8u : 0u));
-	frows = airs_dev_scratch(dev, AIRS_SLOT_ENCIMG + 2, frows_bytes + 16u);
+
+	/* the rows and tables of the largest piece, allocated once: growing them
+	 * between pieces would wait for the stream */
+	for (f = 0; f < N; f += p.count) {
+		size_t need = 0, srows = 0;
+		uint64_t stride, blocks = 0;
+		uint32_t j;
+
+		next_piece(&J, f, &p);
+		if (p.kind == CMP_IMAGE_PIECE_REFUSED)
+			continue;
+		if (p.kind == CMP_IMAGE_PIECE_RUN) {
+			const uint32_t fb = img->frame_bytes[f];
+
+			need = (size_t)p.count * up8(cmp_compress_bound(fb));
+			if (!run_direct(img, f, p.count, sample_bytes, &stride))
+				srows = (size_t)p.count * up16(fb);
+		} else {
+			struct rag_layout L;
+
+			for (j = 0; j < p.count; j++) {
+				need += up8(J.bound[f + j]);
+				blocks += frame_segs(&J, f + j);
+				if (!frame_direct(img, f + j, sample_bytes))
+					srows += up16(img->frame_bytes[f + j]);
+			}
+			rag_layout(p.count, blocks, &L);
+			rag_bytes = L.total > rag_bytes ? L.total : rag_bytes;
+		}
+		frows_bytes = need > frows_bytes ? need : frows_bytes;
+		staged |= srows != 0;
+		rows_bytes = srows > rows_bytes ? srows : rows_bytes;
+	}
+	/* the sticky word, then the offsets of the frames in src, then a ragged piece's tables */
+	rag_at = (8u + (staged ? (size_t)N * 8u : 0u) + 31u) & ~(size_t)31u;
+	J.tables = airs_dev_scratch(J.dev, AIRS_SLOT_ENCIMG, rag_at + rag_bytes);
+	J.frows = airs_dev_scratch(J.dev, AIRS_SLOT_ENCIMG + 2, frows_bytes + 16u);
 	if (staged)
-		rows = airs_dev_scratch(dev, AIRS_SLOT_ENCIMG + 1, rows_bytes);
-	if (!tables || !frows || (staged && !rows))
+		J.rows = airs_dev_scratch(J.dev, AIRS_SLOT_ENCIMG + 1, rows_bytes);
+	if (!J.tables || !J.frows || (staged && !J.rows)) {
+		free(J.bound);
 		return ERRV(GENERIC);
-	d_off = (uint64_t *)(tables + 8u);
+	}
+	J.d_off = (uint64_t *)(J.tables + 8u);
+	J.rag = J.tables + rag_at;
 	/* Straight from the caller's pageable table, as the batch path uploads its
 	 * identifiers (cmp_batch.c): the runtime has staged a pageable source when
 	 * the copy call returns.  The engine's page-locked scratch is no place for
 	 * it: this call does not wait, and the next call on the engine may rewrite
 	 * that scratch while the copy is still queued. */
-	if (staged && airs_dev_h2d(dev, d_off, img->offsets, (size_t)N * 8u))
+	if (staged && airs_dev_h2d(J.dev, J.d_off, img->offsets, (size_t)N * 8u)) {
+		free(J.bound);
 		return ERRV(GENERIC);
-
-	for (f = 0; f < N; f += r.count) {
-		const uint32_t fb = img->frame_bytes[f];
-		const uint32_t refused = frame_refusal(fb, sample_bytes, &bound);
-		struct airs_encode_image q;
-
-		cmp_image_run_next(img->frame_bytes, N, engine->image_chunk, cmp_image_run_row(fb, bound), 0, f, &r);
-		memset(&q, 0, sizeof(q));
-		q.count = r.count;
-		if (!refused) {
-			struct cmp_gpu_batch b;
-
-			memset(&b, 0, sizeof(b));
-			b.type = img->type;
-			if (run_direct(img, &r, sample_bytes, &stride)) {
-				b.src = (const uint8_t *)img->src + img->offsets[f];
-				b.src_stride = stride;
-			} else {
-				q.stage = AIRS_ENCIMG_INGEST;
-				q.src = img->src;
-				q.offsets = d_off + f;
-				q.frame_bytes = fb;
-				q.swap = (img->flags & CMP_GPU_IMG_SRC_BIG_ENDIAN) != 0;
-				q.rows = rows;
-				q.row_bytes = up16(fb);
-				e = airs_dev_encode_image(dev, &q);
-				if (e)
-					return e;
-				b.src = rows;
-				b.src_stride = q.row_bytes;
-			}
-			b.src_size = fb;
-			b.dst = frows;
-			b.dst_stride = (bound + 7u) & ~7u;
-			b.dst_capacity = bound;
-			b.sizes = img->sizes + f;
-			b.flags = img->batch_flags;
-			e = cmp_batch_compress(engine, ctx, 1, r.count, &b);
-			if (e)
-				return e;
-		}
-		q.stage = AIRS_ENCIMG_EMIT;
-		q.frows = frows;
-		q.frow_bytes = (bound + 7u) & ~7u;
-		q.frow_cap = bound;
-		q.sizes = img->sizes + f;
-		q.out_offsets = img->out_offsets + f;
-		q.sticky = (uint32_t *)tables;
-		q.out = img->out;
-		q.out_capacity = img->out_capacity;
-		q.first_run = first_run;
-		q.force = refused;
-		e = airs_dev_encode_image(dev, &q);
-		if (e)
-			return e;
-		first_run = 0;
 	}
-	return 0;
+
+	for (f = 0, e = 0; f < N && !e; f += p.count) {
+		next_piece(&J, f, &p);
+		e = p.kind == CMP_IMAGE_PIECE_RAGGED ? piece_ragged(&J, f, p.count) : piece_run(&J, f, p.count);
+	}
+	free(J.bound);
+	return e;
 }

@@ -671,6 +671,10 @@ uint32_t cmp_gpu_engine_set_option(struct cmp_gpu_engine *engine, uint32_t optio
 		engine->image_chunk = value;
 		return 0;
 	}
+	if (option == CMP_GPU_OPT_IMAGE_RAGGED) { /* how cmp_gpu_compress_image schedules: host-side too */
+		engine->image_ragged = value;
+		return 0;
+	}
 	return airs_dev_set_option(engine->dev, option, value);
 }
 

@@ -2,9 +2,10 @@
  * cmp_image_plan.c -- the host side of cmp_gpu_decompress_image that needs no
  * device: cmp_gpu_frame_table (include/cmp_gpu.h), the walk over an image of
  * back-to-back frames, and the chunk planner; and the run planner of
- * cmp_gpu_compress_image.  Nothing here includes HIP or the device layer, so
- * a stand-alone program links this file alone
- * (tests/sanitize/image_plan_fuzz.c, encode_plan_fuzz.c).
+ * cmp_gpu_compress_image with the piece planner and the block table of its
+ * ragged launches.  Nothing here includes HIP or the device layer, so a
+ * stand-alone program links this file alone
+ * (tests/sanitize/image_plan_fuzz.c, encode_plan_fuzz.c, ragged_plan_fuzz.c).
  */
 #include <stddef.h>
 #include <stdint.h>
@@ -98,4 +99,92 @@ void cmp_image_run_next(const uint32_t *frame_bytes, uint64_t num_frames, uint64
 		count++;
 	run->first = first;
 	run->count = (uint32_t)count;
+}
+
+/* The count of the run cmp_image_run_next cuts at frame f (max_frames 0),
+ * without walking the stretch of equal frames again for every f: *eq_end is
+ * the end of the stretch an earlier call walked (0 at first), and f lies in
+ * that stretch while f < *eq_end. */
+static uint64_t run_count(const uint32_t *frame_bytes, const uint32_t *bound, uint64_t num_frames, uint64_t budget,
+			  uint64_t f, uint64_t *eq_end)
+{
+	const uint64_t row = cmp_image_run_row(frame_bytes[f], bound[f]);
+	uint64_t most = row ? budget / row : CMP_IMAGE_RUN_FRAMES, count;
+
+	if (*eq_end <= f) {
+		uint64_t e = f + 1;
+
+		while (e < num_frames && frame_bytes[e] == frame_bytes[f])
+			e++;
+		*eq_end = e;
+	}
+	if (most > CMP_IMAGE_RUN_FRAMES)
+		most = CMP_IMAGE_RUN_FRAMES;
+	count = *eq_end - f < most ? *eq_end - f : most;
+	return count ? count : 1;
+}
+
+static int run_kept(uint64_t count, uint32_t frame_bytes, uint64_t keep_bytes)
+{
+	return count >= 2 && count * frame_bytes >= keep_bytes;
+}
+
+void cmp_image_piece_next(const uint32_t *frame_bytes, const uint32_t *bound, uint64_t num_frames, uint64_t budget,
+			  uint64_t keep_bytes, uint32_t max_frames, uint64_t first, struct cmp_image_piece *piece)
+{
+	uint64_t eq_end = 0, count, sum, f;
+
+	if (!budget)
+		budget = CMP_IMAGE_CHUNK_DEFAULT;
+	if (!max_frames || max_frames > CMP_IMAGE_RAGGED_FRAMES)
+		max_frames = CMP_IMAGE_RAGGED_FRAMES;
+	piece->first = first;
+	count = run_count(frame_bytes, bound, num_frames, budget, first, &eq_end);
+	if (!bound[first] || run_kept(count, frame_bytes[first], keep_bytes)) {
+		piece->kind = bound[first] ? CMP_IMAGE_PIECE_RUN : CMP_IMAGE_PIECE_REFUSED;
+		piece->count = (uint32_t)count;
+		return;
+	}
+	sum = cmp_image_run_row(frame_bytes[first], bound[first]);
+	for (f = first + 1; f < num_frames && f - first < max_frames; f++) {
+		const uint64_t row = cmp_image_run_row(frame_bytes[f], bound[f]);
+
+		if (!bound[f] || row > budget || sum > budget - row)
+			break;
+		if (run_kept(run_count(frame_bytes, bound, num_frames, budget, f, &eq_end), frame_bytes[f], keep_bytes))
+			break;
+		sum += row;
+	}
+	piece->kind = CMP_IMAGE_PIECE_RAGGED;
+	piece->count = (uint32_t)(f - first);
+}
+
+uint64_t cmp_image_ragged_blocks(const uint32_t *segs, uint32_t count, uint32_t *active,
+				 struct cmp_image_block *blocks)
+{
+	uint64_t total = 0;
+	uint32_t j, live = 0, s;
+
+	for (j = 0; j < count; j++) {
+		total += segs[j];
+		if (blocks && segs[j])
+			active[live++] = j;
+	}
+	if (!blocks)
+		return total;
+	/* round s: the frames that have a segment s, in table order; those that
+	 * have a segment s + 1 too stay for the next round */
+	for (s = 0, total = 0; live; s++) {
+		uint32_t i, keep = 0;
+
+		for (i = 0; i < live; i++) {
+			j = active[i];
+			blocks[total].frame = j;
+			blocks[total++].seg = s;
+			if (segs[j] > s + 1u)
+				active[keep++] = j;
+		}
+		live = keep;
+	}
+	return total;
 }

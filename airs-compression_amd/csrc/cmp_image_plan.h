@@ -55,6 +55,58 @@ uint64_t cmp_image_run_row(uint32_t frame_bytes, uint32_t bound);
 void cmp_image_run_next(const uint32_t *frame_bytes, uint64_t num_frames, uint64_t budget, uint64_t row_bytes,
 			uint32_t max_frames, uint64_t first, struct cmp_image_run *run);
 
+/* ---- ragged pieces (CMP_GPU_OPT_IMAGE_RAGGED) ---- */
+
+/* The built-in keep threshold (option value 1): a run of equal frames with
+ * fewer bytes of samples than this joins a ragged piece instead of taking a
+ * batch launch, a scan and an emit of its own.  Not below 1 MiB: a run's fixed
+ * cost (about 12 us) is more than ten times what even a
+ * twice-slower kernel loses on 1 MiB of samples.  DESIGN.md 3.4.5 has the
+ * table that decides the value. */
+#define CMP_IMAGE_RAGGED_KEEP (1u << 20)
+#define CMP_IMAGE_RAGGED_FRAMES (1u << 20) /* frames per ragged piece at most: the slice of the copies' grids */
+
+enum cmp_image_piece_kind {
+	CMP_IMAGE_PIECE_REFUSED = 0, /* a run of frames the loop's call refuses: the scan alone */
+	CMP_IMAGE_PIECE_RUN = 1,     /* a run of equal frames kept on the batch path */
+	CMP_IMAGE_PIECE_RAGGED = 2   /* frames of any sizes in one ragged launch per pass */
+};
+
+struct cmp_image_piece {
+	uint64_t first;
+	uint32_t count; /* >= 1 */
+	uint32_t kind;  /* enum cmp_image_piece_kind */
+};
+
+/* The piece that starts at frame `first` < num_frames.  bound[f] is frame f's
+ * capacity, 0 for a frame that is refused (equal frames are refused alike).
+ * With R the run cmp_image_run_next cuts at `first` (row_bytes the
+ * cmp_image_run_row of its frames, max_frames 0):
+ *   REFUSED  bound[first] == 0: the piece is R;
+ *   RUN      R has at least 2 frames and count * frame_bytes >= keep_bytes: R;
+ *   RAGGED   otherwise the piece takes frame `first` and then following frames
+ *            while the next frame is not refused, the run that would start at
+ *            it is no kept RUN, the sum of cmp_image_run_row over the piece
+ *            stays within `budget` (0: the default) and the count within
+ *            max_frames (0, or anything above it: CMP_IMAGE_RAGGED_FRAMES). */
+void cmp_image_piece_next(const uint32_t *frame_bytes, const uint32_t *bound, uint64_t num_frames, uint64_t budget,
+			  uint64_t keep_bytes, uint32_t max_frames, uint64_t first, struct cmp_image_piece *piece);
+
+/* one block of a ragged launch: segment `seg` of the piece's frame `frame` */
+struct cmp_image_block {
+	uint32_t frame, seg;
+};
+
+/* The blocks of one ragged launch, in dispatch order: segs[j] is the segment
+ * count of the piece's frame j in this launch (0: the frame belongs to the
+ * other pass).  Ordered by segment index, then frame: every frame's segment 0
+ * in table order, then every frame's segment 1, and so on, so that (frame, s)
+ * always stands after (frame, s - 1) and every (frame, segment) appears once.
+ * `active` is scratch of `count` words.  Returns the number of blocks; with
+ * blocks NULL it only counts (active may be NULL too). */
+uint64_t cmp_image_ragged_blocks(const uint32_t *segs, uint32_t count, uint32_t *active,
+				 struct cmp_image_block *blocks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -751,6 +751,20 @@ bool rice_encode(const KArgs &k, uint32_t pre, hipStream_t s, bool stream);
 bool rice_auto_encode(const KArgs &k, uint32_t pre, hipStream_t s);
 void stream_encode(const KArgs &k, uint32_t sample_bytes, uint32_t pre, uint32_t enc, bool rice, bool full,
 		   uint32_t grid, hipStream_t s);
+// the ragged encode kernel (enc_ragged.hip): frames of different sizes in one
+// launch.  Block b works on desc[b]; the other arrays are indexed by the
+// descriptor's frame (the frame's index in the piece).  Of KArgs it uses dst,
+// status, agg, tail, ticket, epoch, g, outlier_param and img_words.
+struct RaggedTabs {
+	const airs_ragged_desc *desc; // [blocks of the launch], 32-byte aligned
+	const uint64_t *dst_off;      // byte offset of the frame's row in dst (8-byte aligned)
+	const uint32_t *caps;         // the frame's capacity
+	const uint64_t *ids;          // header identifier
+	const uint8_t *seqs;          // header sequence number
+};
+uint32_t ragged_segn(uint32_t sample_bytes);
+void ragged_encode(const KArgs &k, const RaggedTabs &t, uint32_t sample_bytes, uint32_t pre, uint32_t enc, bool rice,
+		   uint32_t grid, hipStream_t s);
 // host-side launch counters (airs_dev_launch_stats, airs_dev.h), one increment
 // at each launch site
 void launch_count(uint32_t which);

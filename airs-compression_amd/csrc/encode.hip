@@ -1838,6 +1838,57 @@ extern "C" uint32_t airs_dev_encode(struct airs_dev_engine *e, const struct airs
 	return 0;
 }
 
+// ---- frames of different sizes in one launch (enc_ragged.hip) ---------------
+
+// ragged launches, the frames they encoded, their blocks (airs_dev_ragged_stats)
+static std::atomic<uint64_t> g_ragged_stats[AIRS_RAGGED_STAT_COUNT];
+
+extern "C" uint32_t airs_dev_ragged_stats(uint64_t *out, uint32_t n)
+{
+	for (uint32_t i = 0; out && i < n && i < AIRS_RAGGED_STAT_COUNT; i++)
+		out[i] = g_ragged_stats[i].load(std::memory_order_relaxed);
+	return AIRS_RAGGED_STAT_COUNT;
+}
+
+extern "C" uint32_t airs_dev_ragged_segment(uint32_t sample_bytes)
+{
+	return ragged_segn(sample_bytes);
+}
+
+extern "C" uint32_t airs_dev_encode_ragged(struct airs_dev_engine *e, const struct airs_ragged *q)
+{
+	if (!e || !q || !q->blocks || !q->frames || q->blocks > 0x7FFFFFFFu || q->slots > 0x7FFFFFFFu)
+		return ERRV(E_GENERIC);
+	if (!q->desc || ((uintptr_t)q->desc & 31u) || !q->dst || !q->dst_off || !q->caps || !q->ids || !q->seqs ||
+	    !q->status)
+		return ERRV(E_GENERIC);
+	if ((q->preprocessing != PRE_NONE && q->preprocessing != PRE_DIFF) || q->encoder_type > ENC_MULTI ||
+	    (q->sample_bytes != 2 && q->sample_bytes != 4))
+		return ERRV(E_PARAMS_INVALID);
+	const uint32_t r = ensure_granules(e, q->slots);
+	if (r)
+		return r;
+	KArgs k;
+	memset(&k, 0, sizeof(k));
+	k.dst = (uint8_t *)q->dst;
+	k.status = q->status;
+	k.agg = e->agg;
+	k.tail = e->tail;
+	k.ticket = e->ticket;
+	k.g = q->encoder_param;
+	k.outlier_param = q->outlier_param;
+	k.img_words = image_words(q->encoder_type, q->encoder_param);
+	k.epoch = next_epoch(e);
+	RaggedTabs t = {q->desc, q->dst_off, q->caps, q->ids, q->seqs};
+	const bool rice = q->encoder_param && (q->encoder_param & (q->encoder_param - 1u)) == 0u;
+	ragged_encode(k, t, q->sample_bytes, q->preprocessing, q->encoder_type, rice, q->blocks, e->stream);
+	HIPCHECK(hipGetLastError());
+	g_ragged_stats[AIRS_RAGGED_STAT_LAUNCHES].fetch_add(1u, std::memory_order_relaxed);
+	g_ragged_stats[AIRS_RAGGED_STAT_FRAMES].fetch_add(q->frames, std::memory_order_relaxed);
+	g_ragged_stats[AIRS_RAGGED_STAT_BLOCKS].fetch_add(q->blocks, std::memory_order_relaxed);
+	return 0;
+}
+
 // ---- MODEL streams in one launch (enc_walk.hip) ----------------------------
 
 // segment-walk workgroups (of 4096 samples) below which the walk takes

@@ -29,6 +29,12 @@
  * Both copies run one workgroup per (frame, 16 KiB tile) and use no LDS.  The
  * sizes are known on the device only, so the emit grid covers the row's
  * capacity and the workgroups past the frame's end return at once.
+ *
+ * A ragged piece (frames of unequal sizes) gives both copies
+ * per-frame tables instead of one stride: the ingest a row offset and a length
+ * per frame (length 0: the frame is read where it lies, its workgroups return
+ * at once), the emit a frame-row offset per frame.  Their grids then cover the
+ * largest frame of the piece.  With null tables the kernels behave as above.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,19 +63,24 @@ struct EncImgArgs {
 	const uint32_t *sizes;  // [frames of the launch]
 	const uint64_t *dof;    // [frames of the launch]: byte offset in out
 	uint8_t *out;
+	// a ragged piece (optional): per-frame row offsets and lengths instead of
+	// row_bytes / frame_bytes, per-frame frame-row offsets instead of frow_bytes
+	const uint64_t *row_off;
+	const uint32_t *row_len;
+	const uint64_t *frow_off;
 };
 
 // Grid: frames of the launch x 16 KiB tiles of a row.
 __global__ __launch_bounds__(IMG_WG) void encimage_ingest_kernel(EncImgArgs a)
 {
 	const uint32_t f = blockIdx.x;
-	const uint32_t len = a.frame_bytes;
+	const uint32_t len = a.row_len ? a.row_len[f] : a.frame_bytes; // (0: a frame read where it lies)
 	const uint32_t fill = (len + 15u) & ~15u;
 	const uint32_t t0 = blockIdx.y * IMG_TILE + threadIdx.x * 16u;
 	if (blockIdx.y * IMG_TILE >= fill)
 		return;
 	const uint8_t *s = a.src + a.off[f], *end = s + len;
-	uint8_t *row = a.rows + (uint64_t)f * a.row_bytes;
+	uint8_t *row = a.rows + (a.row_off ? a.row_off[f] : (uint64_t)f * a.row_bytes);
 	uint4 v[IMG_LINES];
 #pragma unroll
 	for (uint32_t i = 0; i < IMG_LINES; i++) {
@@ -149,7 +160,7 @@ __global__ __launch_bounds__(IMG_WG) void encimage_emit_kernel(EncImgArgs a)
 	const uint32_t bytes = a.sizes[f];
 	if (bytes > ERRV(E_MAX_CODE))
 		return;
-	const uint8_t *row = a.frows + (uint64_t)f * a.frow_bytes;
+	const uint8_t *row = a.frows + (a.frow_off ? a.frow_off[f] : (uint64_t)f * a.frow_bytes);
 	uint8_t *d = a.out + a.dof[f];
 	const uint32_t head = min((uint32_t)((0u - (uintptr_t)d) & 15u), bytes);
 	const uint32_t body = (bytes - head) & ~15u;
@@ -202,7 +213,7 @@ extern "C" uint32_t airs_dev_encode_image(struct airs_dev_engine *e, const struc
 	memset(&a, 0, sizeof(a));
 	if (q->stage == AIRS_ENCIMG_INGEST) {
 		if (!q->src || !q->offsets || !q->rows || !q->frame_bytes || ((uintptr_t)q->rows & 15u) ||
-		    (q->row_bytes & 15u) || q->row_bytes < q->frame_bytes)
+		    (!q->row_len && ((q->row_bytes & 15u) || q->row_bytes < q->frame_bytes)) || !q->row_len != !q->row_off)
 			return ERRV(E_GENERIC);
 		a.src = (const uint8_t *)q->src;
 		a.row_bytes = q->row_bytes;
@@ -214,13 +225,16 @@ extern "C" uint32_t airs_dev_encode_image(struct airs_dev_engine *e, const struc
 		for (uint32_t j = 0; j < q->count; j += ENCIMG_SLICE) {
 			const uint32_t cnt = q->count - j < ENCIMG_SLICE ? q->count - j : ENCIMG_SLICE;
 			a.off = q->offsets + j;
-			a.rows = (uint8_t *)q->rows + (uint64_t)j * q->row_bytes;
+			a.rows = (uint8_t *)q->rows + (q->row_len ? 0u : (uint64_t)j * q->row_bytes);
+			a.row_off = q->row_off ? q->row_off + j : nullptr;
+			a.row_len = q->row_len ? q->row_len + j : nullptr;
 			hipLaunchKernelGGL(encimage_ingest_kernel, dim3(cnt, tiles), dim3(IMG_WG), 0, s, a);
 		}
-		__atomic_fetch_add(&g_encimg_stats[AIRS_ENCIMG_STAT_INGEST], q->count, __ATOMIC_RELAXED);
+		__atomic_fetch_add(&g_encimg_stats[AIRS_ENCIMG_STAT_INGEST], q->row_len ? q->staged : q->count,
+				   __ATOMIC_RELAXED);
 	} else if (q->stage == AIRS_ENCIMG_EMIT) {
 		if (!q->sizes || !q->out_offsets || !q->sticky || !q->out || (!q->force && !q->frows) ||
-		    (q->frow_bytes & 7u) || q->frow_bytes < q->frow_cap)
+		    (!q->frow_off && ((q->frow_bytes & 7u) || q->frow_bytes < q->frow_cap)))
 			return ERRV(E_GENERIC);
 		hipLaunchKernelGGL(encimage_scan_kernel, dim3(1), dim3(IMG_WG), 0, s, q->sizes, q->out_offsets, q->sticky,
 				   q->count, q->out_capacity, q->first_run, q->force);
@@ -234,7 +248,8 @@ extern "C" uint32_t airs_dev_encode_image(struct airs_dev_engine *e, const struc
 				return ERRV(E_GENERIC);
 			for (uint32_t j = 0; j < q->count; j += ENCIMG_SLICE) {
 				const uint32_t cnt = q->count - j < ENCIMG_SLICE ? q->count - j : ENCIMG_SLICE;
-				a.frows = (const uint8_t *)q->frows + (uint64_t)j * q->frow_bytes;
+				a.frows = (const uint8_t *)q->frows + (q->frow_off ? 0u : (uint64_t)j * q->frow_bytes);
+				a.frow_off = q->frow_off ? q->frow_off + j : nullptr;
 				a.sizes = q->sizes + j;
 				a.dof = q->out_offsets + j;
 				hipLaunchKernelGGL(encimage_emit_kernel, dim3(cnt, tiles ? tiles : 1u), dim3(IMG_WG), 0, s,

@@ -103,7 +103,10 @@ void cmp_gpu_engine_destroy(struct cmp_gpu_engine *engine);
  *   CMP_GPU_OPT_IMAGE_CHUNK     (4, defined with cmp_gpu_decompress_image) bytes
  *                               of engine scratch a chunk of that call, or a run
  *                               of cmp_gpu_compress_image, may stage; 0: the
- *                               default, 256 MiB. */
+ *                               default, 256 MiB.
+ *   CMP_GPU_OPT_IMAGE_RAGGED    (5, defined with cmp_gpu_compress_image) frames
+ *                               of unequal sizes share one encode launch there;
+ *                               0: off (the default). */
 #define CMP_GPU_OPT_EXCLUSIVE 1u
 #define CMP_GPU_OPT_WALK_SEGMENT 2u
 #define CMP_GPU_OPT_NO_CONTEXT_WALK 3u
@@ -362,12 +365,29 @@ uint64_t cmp_gpu_frame_table(const void *image, uint64_t size, uint64_t *offsets
  * constant that is at least frame_bytes and a multiple of the sample size is
  * read where it is; every other run is first copied into aligned native rows.
  *
+ * CMP_GPU_OPT_IMAGE_RAGGED (engine option; 0, the default: off) changes only
+ * how the call schedules this work; no result depends on its value.  It
+ * applies when the context keeps no state in its work buffer (no MODEL pass,
+ * no IWT), the checksum and the uncompressed fallback are disabled and
+ * batch_flags is 0; any other call takes the runs above whatever the option
+ * says.  The table is then cut into pieces.  A run of at least 2 frames whose
+ * samples take at least the keep threshold (value 1: the built-in one, 1 MiB;
+ * any other value: that many bytes) stays a run as above, and so do frames
+ * that are refused.  Every other frame joins a ragged piece: consecutive
+ * frames of any sizes, while their staging rows fit CMP_GPU_OPT_IMAGE_CHUNK
+ * and their number 2^20, encoded by one launch per pass (two when
+ * secondary_iterations is set), with one offset scan and one copy into out for
+ * the whole piece.  In a ragged piece a native-endian frame whose address is
+ * a multiple of the sample size is read where it is, whatever its neighbours'
+ * offsets; the others are copied into aligned native rows first.
+ *
  * Synchronisation.  The call is asynchronous on the engine's stream exactly
  * where cmp_gpu_compress with dst_capacity = cmp_compress_bound would be for
  * each run, synchronises where that call does and nowhere else (engine scratch
  * that has to grow waits for the stream, as there); sizes, out_offsets and out
  * are valid after cmp_gpu_synchronize.  Build-defined extension.
  */
+#define CMP_GPU_OPT_IMAGE_RAGGED 5u /* cmp_gpu_engine_set_option: 0 off, 1 on, else on with that keep threshold in bytes */
 #define CMP_GPU_IMG_SRC_BIG_ENDIAN 0x1u /* samples in src are big-endian 16-bit words (sample files) */
 
 struct cmp_gpu_encode_image {

@@ -19,6 +19,15 @@ Kernel times come from a profiler run of this script with --once VARIANT
 are the one cold call); profiles/image_encode.json holds them beside the table.
 
     python scripts/image_encode_bench.py --out profiles/image_encode.json
+
+--ragged measures CMP_GPU_OPT_IMAGE_RAGGED under the same
+discipline: 1024 u16 frames of 64 Ki + 2 i samples (every size differs), native
+and aligned or big-endian, with the option off (1024 runs) and on; then, for
+the built-in keep threshold, runs of 2 .. 1024 equal frames of 64 Ki samples on
+the run path against the same frames in a ragged piece (option value
+0xFFFFFFFF: no run is kept).  --once takes VARIANT names of that mode too.
+
+    python scripts/image_encode_bench.py --ragged --out profiles/image_encode_ragged.json
 """
 import argparse
 import importlib.util
@@ -33,6 +42,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG_DIR = os.path.join(ROOT, "airs-compression_amd")
 FRAMES, N, G = 1024, 65536, 32
 VARIANTS = ("batch_pack", "image_direct", "image_odd", "image_be")
+RAGGED_VARIANTS = ("native_off", "native_on", "be_off", "be_on")
+KEEP_RUNS = (2, 8, 32, 128, 1024)
+NO_KEEP = 0xFFFFFFFF  # option value: on, and no run of equal frames is large enough to be kept
 
 
 def load_pkg():
@@ -44,12 +56,124 @@ def load_pkg():
     return mod
 
 
+def stats(ts):
+    return {"median": statistics.median(ts), "min": min(ts), "max": max(ts), "all": ts}
+
+
+def ragged_main(a):
+    """The ragged option's two measurements (module docstring)."""
+    import torch
+    pkg = load_pkg()
+    api = pkg.cmpapi
+    lib = pkg.load()
+    assert lib.gpu_available(), "no HIP device"
+    eng = lib.engine()
+    ns = [N + 2 * i for i in range(FRAMES)]
+    stride = (2 * ns[-1] + 15) // 16 * 16  # bytes between frames: every frame 16-byte aligned
+    native = torch.empty(FRAMES * stride // 2 + 8, dtype=torch.int16, device="cuda")
+    assert eng.synthesize(native.data_ptr(), 2, 0xA1A5, 0, stride // 2, FRAMES, stride, 32) == 0
+    torch.cuda.synchronize()
+    host = native.cpu().numpy()[:FRAMES * stride // 2].view(np.uint16)
+    be = torch.from_numpy(host.byteswap().view(np.uint8).copy()).cuda()
+    offs = np.arange(FRAMES, dtype=np.uint64) * stride
+    fbs = np.array([2 * n for n in ns], dtype=np.uint32)
+    eq_offs = np.arange(FRAMES, dtype=np.uint64) * (2 * N)  # the keep workload: equal frames, back to back
+    eq_fbs = np.full(FRAMES, 2 * N, dtype=np.uint32)
+    cap = lib.compress_bound(int(fbs[-1]))
+    out = torch.zeros(FRAMES * cap, dtype=torch.uint8, device="cuda")
+    ooffs = torch.zeros(FRAMES + 1, dtype=torch.int64, device="cuda")
+    sizes = torch.zeros(FRAMES, dtype=torch.int32, device="cuda")
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
+    prm = api.CmpParams(primary_preprocessing=1, primary_encoder_type=1, primary_encoder_param=G)
+    ctxs = pkg.context_array(1)
+
+    def image(src, flags, option, o, f, count=FRAMES):
+        def call():
+            assert eng.set_option(pkg.OPT_IMAGE_RAGGED, option) == 0
+            rc = eng.compress_image(ctxs[0], "u16", src.data_ptr(), src.numel() * src.element_size(), o[:count],
+                                    f[:count], out.data_ptr(), FRAMES * cap, ooffs.data_ptr(), sizes.data_ptr(), 0,
+                                    flags)
+            assert rc == 0, api.error_name(rc)
+        call.count = count
+        return call
+
+    calls = {"native_off": image(native, 0, 0, offs, fbs), "native_on": image(native, 0, 1, offs, fbs),
+             "be_off": image(be, pkg.IMG_SRC_BIG_ENDIAN, 0, offs, fbs),
+             "be_on": image(be, pkg.IMG_SRC_BIG_ENDIAN, 1, offs, fbs)}
+    for c in KEEP_RUNS:
+        calls[f"run_{c}"] = image(native, 0, 0, eq_offs, eq_fbs, c)
+        calls[f"ragged_{c}"] = image(native, 0, NO_KEEP, eq_offs, eq_fbs, c)
+
+    def timed(fn):
+        assert not api.is_error(lib.initialise(ctxs[0], prm))
+        flush.fill_(1)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3  # us
+
+    def frames_of(count):
+        b, o, sz = out.cpu().numpy(), ooffs.cpu().numpy(), sizes.cpu().numpy().astype(np.int64)
+        assert (sz[:count] > 0).all() and int(o[count]) == int(sz[:count].sum())
+        return [bytes(b[int(o[f]):int(o[f]) + 8]) + bytes(b[int(o[f]) + 14:int(o[f]) + int(sz[f])])
+                for f in range(count)], int(sz[:count].sum())
+
+    # warm up, and the variants of a workload against each other: the same
+    # frames, identifiers excepted (header bytes 8..13 come from the clock)
+    want, total = {}, {}
+    for name, fn in calls.items():
+        for _ in range(2):
+            assert not api.is_error(lib.initialise(ctxs[0], prm))
+            fn()
+        assert eng.synchronize() == 0
+        key = "ragged" if name in RAGGED_VARIANTS else name.split("_")[1]
+        got, total[key] = frames_of(fn.count)
+        assert got == want.setdefault(key, got), f"{name} differs"
+    if a.once:
+        timed(calls[a.once])
+        return
+    res = {"workload": {"frames": FRAMES, "samples_per_frame": "65536 + 2 i", "preprocessing": "DIFF",
+                        "encoder": "GOLOMB_ZERO", "g": G, "sample_bytes": int(fbs.sum()),
+                        "compressed_bytes": total["ragged"], "cold": True, "reps": a.reps}}
+    t = {name: [] for name in calls}
+    for _ in range(a.reps):
+        for name in RAGGED_VARIANTS:
+            t[name].append(timed(calls[name]))
+    for _ in range(a.reps):
+        for name in calls:
+            if name not in RAGGED_VARIANTS:
+                t[name].append(timed(calls[name]))
+    for name in RAGGED_VARIANTS:
+        res[name + "_us"] = stats(t[name])
+    for kind in ("native", "be"):
+        off, on = res[kind + "_off_us"], res[kind + "_on_us"]
+        res[kind + "_off_over_on"] = off["median"] / on["median"]
+        res[kind + "_ranges_overlap"] = not (on["max"] < off["min"] or off["max"] < on["min"])
+    res["keep"] = {"workload": "runs of equal frames of 65536 u16 samples, native and aligned", "runs": {}}
+    for c in KEEP_RUNS:
+        run, rag = stats(t[f"run_{c}"]), stats(t[f"ragged_{c}"])
+        res["keep"]["runs"][str(c)] = {"sample_bytes": c * 2 * N, "run_path_us": run, "ragged_path_us": rag,
+                                       "run_not_slower": run["median"] <= rag["median"],
+                                       "ranges_overlap": not (run["max"] < rag["min"] or rag["max"] < run["min"])}
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--out")
-    ap.add_argument("--once", choices=VARIANTS, help="warm up, then one cold call (for a profiler)")
+    ap.add_argument("--ragged", action="store_true", help="the CMP_GPU_OPT_IMAGE_RAGGED measurements")
+    ap.add_argument("--once", help="warm up, then one cold call of this variant (for a profiler)")
     a = ap.parse_args()
+    if a.ragged:
+        return ragged_main(a)
+    assert a.once is None or a.once in VARIANTS, a.once
     import torch
     pkg = load_pkg()
     api = pkg.cmpapi
