@@ -33,6 +33,8 @@ OPT_IMAGE_CHUNK = 4  # CMP_GPU_OPT_IMAGE_CHUNK: bytes of staging per chunk of de
 # CMP_GPU_OPT_IMAGE_RAGGED: compress_image encodes frames of unequal sizes in one launch (0: off, 1: on,
 # any other value: on with that keep threshold in bytes)
 OPT_IMAGE_RAGGED = 5
+# CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM: 1 lets checksum-enabled contexts take those launches too (0: off)
+OPT_IMAGE_RAGGED_CHECKSUM = 6
 IMG_MODEL_IN = 0x1  # CMP_GPU_IMG_MODEL_IN (cmp_gpu_decompress_image)
 IMG_BIG_ENDIAN = 0x2  # CMP_GPU_IMG_BIG_ENDIAN
 IMG_SRC_BIG_ENDIAN = 0x1  # CMP_GPU_IMG_SRC_BIG_ENDIAN (cmp_gpu_compress_image)
@@ -312,7 +314,7 @@ class GpuEngine:
 
     def set_option(self, option: int, value: int) -> int:
         """cmp_gpu_engine_set_option (OPT_EXCLUSIVE, OPT_WALK_SEGMENT, OPT_NO_CONTEXT_WALK, OPT_IMAGE_CHUNK,
-        OPT_IMAGE_RAGGED)."""
+        OPT_IMAGE_RAGGED, OPT_IMAGE_RAGGED_CHECKSUM)."""
         return int(self.lib.lib.cmp_gpu_engine_set_option(self.handle, option, value))
 
     def close(self):

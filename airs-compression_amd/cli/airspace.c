@@ -344,6 +344,7 @@ static int dev_open(struct dev *d)
 	}
 	/* files of unequal sizes share one encode launch (no result depends on it) */
 	(void)cmp_gpu_engine_set_option(d->eng, CMP_GPU_OPT_IMAGE_RAGGED, 1);
+	(void)cmp_gpu_engine_set_option(d->eng, CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM, 1); /* with checksum_enabled too */
 	return 0;
 }
 

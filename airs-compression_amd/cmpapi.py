@@ -41,6 +41,8 @@ GPU_STEPWISE = 0x4
 GPU_REPORT_DRAWS = 0x8
 # cmp_gpu_engine_set_option: frames of unequal sizes of cmp_gpu_compress_image in one launch
 GPU_OPT_IMAGE_RAGGED = 5
+# the same for checksum-enabled contexts (0 or 1)
+GPU_OPT_IMAGE_RAGGED_CHECKSUM = 6
 
 
 def err_value(name: str) -> int:

@@ -386,7 +386,8 @@ uint32_t airs_dev_encode_image(struct airs_dev_engine *e, const struct airs_enco
 
 /* One ragged encode launch (enc_ragged.hip; cmp_gpu_compress_image with
  * CMP_GPU_OPT_IMAGE_RAGGED, planned by cmp_image_plan.c): frames of different
- * sizes, one pass (NONE or DIFF, any coder, no model, no checksum).  Block b
+ * sizes, one pass (NONE or DIFF, any coder, no model; a checksum only as the
+ * four bytes of `checksums`, computed before the launch).  Block b
  * of the launch encodes segment desc[b].seg of the frame desc[b] describes;
  * the blocks of a frame stand in ascending segment order.  The frame arrays
  * are indexed by desc[b].frame.  Granule slots desc[b].slot0 + seg lie below
@@ -413,6 +414,8 @@ struct airs_ragged {
 	const uint8_t *seqs;     /* device */
 	uint32_t preprocessing, encoder_type, encoder_param, outlier_param;
 	uint32_t *status;        /* device: frame size or error value */
+	const uint32_t *checksums; /* device, per frame, or NULL: frame j ends with checksums[j] big-endian
+				    * (clipped to its capacity), 4 bytes larger, the header's checksum bit set */
 };
 uint32_t airs_dev_encode_ragged(struct airs_dev_engine *e, const struct airs_ragged *q);
 /* samples per segment of the ragged kernel for samples of sample_bytes bytes */
@@ -429,6 +432,43 @@ enum airs_ragged_stat {
 	AIRS_RAGGED_STAT_COUNT = 3
 };
 uint32_t airs_dev_ragged_stats(uint64_t *out, uint32_t n);
+
+/* XXH32 (seed 419764627) over frames of different sizes that lie anywhere
+ * (ck_ragged.hip): out[j] is what airs_dev_checksum gives for
+ * the n[j] samples at src[j], as big-endian 16-bit words (of 4-byte samples the
+ * low halves).  A product kernel writes frame j's stripes x P2 to the engine's
+ * checksum-products scratch at byte off[j]; a chain kernel, four lanes per
+ * frame and sixteen frames per wave, consumes them.  The host lays the
+ * products out (cmp_image_ck_layout, cmp_image_plan.h): `bytes` is their sum,
+ * blocks the product kernel's workgroups.  Everything is queued; nothing
+ * synchronises unless the scratch has to grow. */
+struct airs_ragged_ck_block {
+	uint32_t frame, qb; /* round quads [256 qb, 256 qb + 256) of the frame (struct cmp_image_ck_block) */
+};
+struct airs_ragged_ck {
+	uint32_t sample_bytes;  /* 2 or 4 */
+	uint32_t frames;
+	const uint64_t *src;    /* device [frames]: address of the frame's first sample, a multiple of
+				 * sample_bytes at any 16-byte phase */
+	const uint32_t *n;      /* device [frames]: samples, >= 1 */
+	const uint64_t *off;    /* device [frames]: byte offset of the frame's products, a multiple of 16 */
+	uint64_t bytes;         /* products of all frames */
+	const struct airs_ragged_ck_block *blocks; /* device [num_blocks] */
+	uint32_t num_blocks;    /* may be 0: no frame has 8 samples */
+	uint32_t *out;          /* device [frames] */
+};
+uint32_t airs_dev_checksum_ragged(struct airs_dev_engine *e, const struct airs_ragged_ck *q);
+
+/* Host-side counters of the process: ragged checksum launches (calls of
+ * airs_dev_checksum_ragged) and the frames they covered.  Copies the first
+ * min(n, AIRS_RAGGED_CK_STAT_COUNT) counters to out and returns
+ * AIRS_RAGGED_CK_STAT_COUNT.  For tests; nothing in the library reads them. */
+enum airs_ragged_ck_stat {
+	AIRS_RAGGED_CK_STAT_LAUNCHES = 0,
+	AIRS_RAGGED_CK_STAT_FRAMES = 1,
+	AIRS_RAGGED_CK_STAT_COUNT = 2
+};
+uint32_t airs_dev_ragged_ck_stats(uint64_t *out, uint32_t n);
 
 /* Host-side counters of the process, counted where the kernels are launched:
  * frames that went through the ingest copy (a run read where it lies adds

@@ -13,7 +13,10 @@
  * the table is cut into pieces instead (cmp_image_piece_next): refused frames
  * and large runs of equal frames go the same way as above, every other frame
  * joins a ragged piece, which is one ingest, one encode launch per pass
- * (enc_ragged.hip), one scan and one emit.
+ * (enc_ragged.hip), one scan and one emit.  With
+ * CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM a checksum-enabled context takes the
+ * pieces too: one ragged XXH32 per piece (ck_ragged.hip) ahead of its encode
+ * launches, which append the four bytes.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -64,6 +67,7 @@ struct image_job {
 	uint32_t *bound;   /* host [num_frames], 0 for a refused frame: ragged calls only (else NULL) */
 	uint64_t keep;     /* the keep threshold of a ragged call */
 	uint32_t seg;      /* samples per segment of the ragged kernel */
+	uint32_t ck;       /* the ragged pieces carry checksums */
 	/* engine scratch */
 	uint8_t *tables;   /* the sticky word, then d_off, then the ragged tables */
 	uint64_t *d_off;   /* the offsets of the frames in src */
@@ -127,12 +131,17 @@ static void next_piece(const struct image_job *J, uint64_t f, struct cmp_image_p
 
 /* The device tables of one ragged piece of cnt frames and `blocks` blocks, as
  * byte offsets into one region that a single copy uploads: the descriptors of
- * both passes' launches, then the per-frame arrays. */
+ * both passes' launches, then the per-frame arrays.  With ck_blocks != NULL the
+ * piece carries checksums: the tables of airs_dev_checksum_ragged (sample
+ * address, product offset, product workgroups, sample count) and its output,
+ * which the encode launches read. */
 struct rag_layout {
-	size_t desc, dst_off, ids, row_off, caps, row_len, seqs, total;
+	size_t desc, dst_off, ids, row_off, ck_src, ck_off, ck_blocks, caps, row_len, ck_n, ck_out, seqs, total;
 };
 
-static void rag_layout(uint32_t cnt, uint64_t blocks, struct rag_layout *L)
+_Static_assert(sizeof(struct cmp_image_ck_block) == sizeof(struct airs_ragged_ck_block), "one table for both");
+
+static void rag_layout(uint32_t cnt, uint64_t blocks, const uint64_t *ck_blocks, struct rag_layout *L)
 {
 	size_t at = 0;
 
@@ -144,10 +153,20 @@ static void rag_layout(uint32_t cnt, uint64_t blocks, struct rag_layout *L)
 	at += (size_t)cnt * 8u;
 	L->row_off = at;
 	at += (size_t)cnt * 8u;
+	L->ck_src = at;
+	at += ck_blocks ? (size_t)cnt * 8u : 0u;
+	L->ck_off = at;
+	at += ck_blocks ? (size_t)cnt * 8u : 0u;
+	L->ck_blocks = at;
+	at += ck_blocks ? (size_t)*ck_blocks * sizeof(struct cmp_image_ck_block) : 0u;
 	L->caps = at;
 	at += (size_t)cnt * 4u;
 	L->row_len = at;
 	at += (size_t)cnt * 4u;
+	L->ck_n = at;
+	at += ck_blocks ? (size_t)cnt * 4u : 0u;
+	L->ck_out = at;
+	at += ck_blocks ? (size_t)cnt * 4u : 0u;
 	L->seqs = at;
 	at += cnt;
 	L->total = (at + 31u) & ~(size_t)31u;
@@ -257,12 +276,15 @@ static uint32_t piece_ragged(struct image_job *J, uint64_t first, uint32_t cnt)
 	uint32_t j, g, e = ERRV(GENERIC), staged = 0, max_len = 0, max_cap = 0, slots = 0;
 	uint64_t gfirst[2] = {0, 0}, gblocks[2] = {0, 0};
 	uint32_t gframes[2] = {0, 0}, gmember[2] = {0, 0};
+	uint64_t ck_blocks = 0, ck_bytes = 0;
 
 	for (j = 0; j < cnt; j++)
 		blocks += frame_segs(J, first + j);
-	if (blocks > 0x7FFFFFFFu)
+	if (J->ck)
+		ck_bytes = cmp_image_ck_layout(img->frame_bytes + first, sb, cnt, NULL, NULL, &ck_blocks);
+	if (blocks > 0x7FFFFFFFu || ck_blocks > 0x7FFFFFFFu)
 		return ERRV(GENERIC);
-	rag_layout(cnt, blocks, &L);
+	rag_layout(cnt, blocks, J->ck ? &ck_blocks : NULL, &L);
 	hb = calloc(1, L.total);
 	pass = malloc((size_t)cnt * sizeof(*pass));
 	blk = malloc((size_t)(blocks ? blocks : 1u) * sizeof(*blk));
@@ -321,6 +343,20 @@ static uint32_t piece_ragged(struct image_job *J, uint64_t first, uint32_t cnt)
 		staged++;
 		max_len = fb > max_len ? fb : max_len;
 	}
+	/* the checksum reads what the descriptors below point at: a staged frame's
+	 * native row, a direct frame where it lies */
+	if (J->ck) {
+		uint64_t *ck_src = (uint64_t *)(hb + L.ck_src);
+		uint32_t *ck_n = (uint32_t *)(hb + L.ck_n);
+
+		(void)cmp_image_ck_layout(img->frame_bytes + first, sb, cnt, (uint64_t *)(hb + L.ck_off),
+					  (struct cmp_image_ck_block *)(hb + L.ck_blocks), NULL);
+		for (j = 0; j < cnt; j++) {
+			ck_src[j] = row_len[j] ? (uint64_t)(uintptr_t)J->rows + row_off[j]
+					       : (uint64_t)(uintptr_t)img->src + img->offsets[first + j];
+			ck_n[j] = img->frame_bytes[first + j] / sb;
+		}
+	}
 	/* the launches: the primary pass's frames (sequence number 0), then the secondary's */
 	for (g = 0; g < 2; g++) {
 		uint64_t nb, i;
@@ -370,6 +406,24 @@ static uint32_t piece_ragged(struct image_job *J, uint64_t first, uint32_t cnt)
 		if (e)
 			goto out;
 	}
+	/* one XXH32 launch pair for the frames of both passes: it does not depend on the pass */
+	if (J->ck) {
+		struct airs_ragged_ck c;
+
+		memset(&c, 0, sizeof(c));
+		c.sample_bytes = sb;
+		c.frames = cnt;
+		c.src = (const uint64_t *)(J->rag + L.ck_src);
+		c.n = (const uint32_t *)(J->rag + L.ck_n);
+		c.off = (const uint64_t *)(J->rag + L.ck_off);
+		c.bytes = ck_bytes;
+		c.blocks = (const struct airs_ragged_ck_block *)(J->rag + L.ck_blocks);
+		c.num_blocks = (uint32_t)ck_blocks;
+		c.out = (uint32_t *)(J->rag + L.ck_out);
+		e = airs_dev_checksum_ragged(J->dev, &c);
+		if (e)
+			goto out;
+	}
 	for (g = 0; g < 2; g++) {
 		const struct pass *p = &pass[gmember[g]];
 		struct airs_ragged r;
@@ -392,6 +446,7 @@ static uint32_t piece_ragged(struct image_job *J, uint64_t first, uint32_t cnt)
 		r.encoder_param = p->par;
 		r.outlier_param = p->outlier_param;
 		r.status = img->sizes + first;
+		r.checksums = J->ck ? (const uint32_t *)(J->rag + L.ck_out) : NULL;
 		e = airs_dev_encode_ragged(J->dev, &r);
 		if (e)
 			goto out;
@@ -406,8 +461,9 @@ out:
 }
 
 /* The ragged path applies: the option is on, the frames of the context are
- * independent (no state in the work buffer), no frame can fall back, nothing
- * needs the checksum's own two launches or the batch path's flags, and the
+ * independent (no state in the work buffer), no frame can fall back, a
+ * checksum has been opted in (CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM: the pieces
+ * then take the ragged XXH32), nothing needs the batch path's flags, and the
  * context's passes are ones the prologue accepts (tried on a copy, with the
  * draws only counted). */
 static int ragged_applies(const struct image_job *J)
@@ -418,8 +474,8 @@ static int ragged_applies(const struct image_job *J)
 	uint32_t drawn = 0;
 	uint64_t dummy[4];
 
-	if (!J->engine->image_ragged || work_buf_state(P) || P->checksum_enabled || P->uncompressed_fallback_enabled ||
-	    J->img->batch_flags)
+	if (!J->engine->image_ragged || work_buf_state(P) || (P->checksum_enabled && !J->engine->image_ragged_ck) ||
+	    P->uncompressed_fallback_enabled || J->img->batch_flags)
 		return 0;
 	c.sequence_number = 0;
 	if (is_err(engine_prologue(&c, dummy, HDR_MAX_SIZE, 1, &p, &drawn)))
@@ -480,6 +536,7 @@ uint32_t cmp_gpu_compress_image(struct cmp_gpu_engine *engine, struct cmp_contex
 			(void)frame_refusal(img->frame_bytes[f], sample_bytes, &J.bound[f]);
 		J.keep = engine->image_ragged == 1u ? CMP_IMAGE_RAGGED_KEEP : engine->image_ragged;
 		J.seg = airs_dev_ragged_segment(sample_bytes);
+		J.ck = ctx->params.checksum_enabled != 0;
 	}
 
 	/* the rows and tables of the largest piece, allocated once: growing them
@@ -500,6 +557,7 @@ uint32_t cmp_gpu_compress_image(struct cmp_gpu_engine *engine, struct cmp_contex
 				srows = (size_t)p.count * up16(fb);
 		} else {
 			struct rag_layout L;
+			uint64_t ck_blocks = 0;
 
 			for (j = 0; j < p.count; j++) {
 				need += up8(J.bound[f + j]);
@@ -507,7 +565,9 @@ uint32_t cmp_gpu_compress_image(struct cmp_gpu_engine *engine, struct cmp_contex
 				if (!frame_direct(img, f + j, sample_bytes))
 					srows += up16(img->frame_bytes[f + j]);
 			}
-			rag_layout(p.count, blocks, &L);
+			if (J.ck)
+				(void)cmp_image_ck_layout(img->frame_bytes + f, sample_bytes, p.count, NULL, NULL, &ck_blocks);
+			rag_layout(p.count, blocks, J.ck ? &ck_blocks : NULL, &L);
 			rag_bytes = L.total > rag_bytes ? L.total : rag_bytes;
 		}
 		frows_bytes = need > frows_bytes ? need : frows_bytes;

@@ -11,6 +11,7 @@ struct cmp_gpu_engine {
 	struct airs_dev_engine *dev;
 	uint32_t image_chunk; /* CMP_GPU_OPT_IMAGE_CHUNK (cmp_decode_image.c, cmp_encode_image.c); 0: the default */
 	uint32_t image_ragged; /* CMP_GPU_OPT_IMAGE_RAGGED (cmp_encode_image.c): 0 off, 1 on, else the keep threshold in bytes */
+	uint32_t image_ragged_ck; /* CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM (cmp_encode_image.c): 0 or 1 */
 };
 
 /* The encoder's own parameter checks (reference encoder.c:185-224), cmp_host.c:

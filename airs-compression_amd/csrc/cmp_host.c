@@ -675,6 +675,12 @@ uint32_t cmp_gpu_engine_set_option(struct cmp_gpu_engine *engine, uint32_t optio
 		engine->image_ragged = value;
 		return 0;
 	}
+	if (option == CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM) { /* whether that schedule takes checksum-enabled contexts */
+		if (value > 1u)
+			return ERRV(PARAMS_INVALID);
+		engine->image_ragged_ck = value;
+		return 0;
+	}
 	return airs_dev_set_option(engine->dev, option, value);
 }
 

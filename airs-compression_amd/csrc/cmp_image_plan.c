@@ -3,9 +3,11 @@
  * device: cmp_gpu_frame_table (include/cmp_gpu.h), the walk over an image of
  * back-to-back frames, and the chunk planner; and the run planner of
  * cmp_gpu_compress_image with the piece planner and the block table of its
- * ragged launches.  Nothing here includes HIP or the device layer, so a
- * stand-alone program links this file alone
- * (tests/sanitize/image_plan_fuzz.c, encode_plan_fuzz.c, ragged_plan_fuzz.c).
+ * ragged launches, and the layout of the ragged checksum's products.
+ * Nothing here includes HIP or the device layer, so a stand-alone program
+ * links this file alone
+ * (tests/sanitize/image_plan_fuzz.c, encode_plan_fuzz.c, ragged_plan_fuzz.c,
+ * ragged_ck_layout_fuzz.c).
  */
 #include <stddef.h>
 #include <stdint.h>
@@ -187,4 +189,37 @@ uint64_t cmp_image_ragged_blocks(const uint32_t *segs, uint32_t count, uint32_t 
 		live = keep;
 	}
 	return total;
+}
+
+uint64_t cmp_image_ck_region(uint32_t n)
+{
+	const uint64_t stripes = n / 8u;
+
+	return (stripes + 3u) / 4u * CMP_IMAGE_CK_QUAD;
+}
+
+uint64_t cmp_image_ck_layout(const uint32_t *frame_bytes, uint32_t sample_bytes, uint32_t count, uint64_t *off,
+			     struct cmp_image_ck_block *blocks, uint64_t *num_blocks)
+{
+	uint64_t at = 0, nb = 0;
+	uint32_t j;
+
+	for (j = 0; j < count; j++) {
+		const uint64_t region = cmp_image_ck_region(frame_bytes[j] / sample_bytes);
+		const uint64_t quads = region / CMP_IMAGE_CK_QUAD;
+		uint64_t qb;
+
+		if (off)
+			off[j] = at;
+		at += region;
+		for (qb = 0; qb * CMP_IMAGE_CK_BLOCK_QUADS < quads; qb++, nb++) {
+			if (blocks) {
+				blocks[nb].frame = j;
+				blocks[nb].qb = (uint32_t)qb;
+			}
+		}
+	}
+	if (num_blocks)
+		*num_blocks = nb;
+	return at;
 }

@@ -107,6 +107,35 @@ struct cmp_image_block {
 uint64_t cmp_image_ragged_blocks(const uint32_t *segs, uint32_t count, uint32_t *active,
 				 struct cmp_image_block *blocks);
 
+/* ---- the ragged checksum's products (CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM) ---- */
+
+/* The XXH32 of a frame of n samples consumes n / 8 stripes of 16 bytes; the
+ * product kernel writes them x P2 in round quads of 64 bytes (accumulator q's
+ * four rounds at bytes 16 q of the quad), so a frame's region is its stripes
+ * rounded up to a quad: at most 2 n + 48 bytes, nothing for n < 8. */
+#define CMP_IMAGE_CK_QUAD 64u          /* bytes of one round quad */
+#define CMP_IMAGE_CK_BLOCK_QUADS 256u  /* round quads one product workgroup forms */
+
+/* one workgroup of the product kernel: round quads [256 qb, 256 qb + 256) of `frame` */
+struct cmp_image_ck_block {
+	uint32_t frame, qb;
+};
+
+/* bytes of the products of a frame of n samples (a multiple of 64) */
+uint64_t cmp_image_ck_region(uint32_t n);
+
+/* The products of a piece's `count` frames (frame j has frame_bytes[j] /
+ * sample_bytes samples, at least 1) back to back in table order: off[j] is
+ * frame j's byte offset (a multiple of 64), the regions do not overlap, the
+ * return value is their sum, which the caller allocates.  blocks receives the
+ * product workgroups, frame by frame (a frame under 8 samples has none), and
+ * *num_blocks their number.  off and blocks may be NULL: it only counts.
+ * The chain kernel takes the frames in table order: a wave of sixteen frames
+ * lasts as long as its longest, whatever the order, and the waves of a piece
+ * run side by side, so an order by size was not built. */
+uint64_t cmp_image_ck_layout(const uint32_t *frame_bytes, uint32_t sample_bytes, uint32_t count, uint64_t *off,
+			     struct cmp_image_ck_block *blocks, uint64_t *num_blocks);
+
 #ifdef __cplusplus
 }
 #endif

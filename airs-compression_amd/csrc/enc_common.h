@@ -761,6 +761,7 @@ struct RaggedTabs {
 	const uint32_t *caps;         // the frame's capacity
 	const uint64_t *ids;          // header identifier
 	const uint8_t *seqs;          // header sequence number
+	const uint32_t *checksums;    // the frame's XXH32, appended to it, or nullptr: no checksum
 };
 uint32_t ragged_segn(uint32_t sample_bytes);
 void ragged_encode(const KArgs &k, const RaggedTabs &t, uint32_t sample_bytes, uint32_t pre, uint32_t enc, bool rice,

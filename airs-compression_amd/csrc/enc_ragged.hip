@@ -462,12 +462,19 @@ __global__ __launch_bounds__(EWG) void ragged_kernel(KArgs a, RaggedTabs t)
 		}
 	}
 
-	// ---- frame epilogue: header, status ----------------------------------
+	// ---- frame epilogue: checksum (when the launch has one), header, status --
 	if (is_last && tid == 0) {
-		const uint32_t size = (P + A + 7u) >> 3;
+		const uint32_t payload_bytes = (P + A + 7u) >> 3;
+		const uint32_t size = payload_bytes + (t.checksums ? 4u : 0u);
+		if (t.checksums) { // as encode_kernel's epilogue: big-endian, clipped to the capacity
+			const uint32_t ck = t.checksums[frame];
+			for (uint32_t b = 0; b < 4u; b++)
+				if (payload_bytes + b < cap)
+					fdst[payload_bytes + b] = (uint8_t)(ck >> (24u - 8u * b));
+		}
 		uint32_t h[5];
-		header_words(h, size, 2u * n, t.ids[frame], t.seqs[frame], PRE, 0u, ENC, 0u, ENC == ENC_RAW ? 0u : gpar,
-			     ENC == ENC_RAW ? 0u : cd.outlier);
+		header_words(h, size, 2u * n, t.ids[frame], t.seqs[frame], PRE, t.checksums ? 1u : 0u, ENC, 0u,
+			     ENC == ENC_RAW ? 0u : gpar, ENC == ENC_RAW ? 0u : cd.outlier);
 		const uint32_t hwords = EXT_HDR ? 5u : 4u;
 		if (((uintptr_t)fdst & 7u) == 0u && cap >= 4u * hwords) {
 			*reinterpret_cast<uint2 *>(fdst) = make_uint2(bswap32(h[0]), bswap32(h[1]));

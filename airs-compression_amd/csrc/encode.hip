@@ -1879,7 +1879,7 @@ extern "C" uint32_t airs_dev_encode_ragged(struct airs_dev_engine *e, const stru
 	k.outlier_param = q->outlier_param;
 	k.img_words = image_words(q->encoder_type, q->encoder_param);
 	k.epoch = next_epoch(e);
-	RaggedTabs t = {q->desc, q->dst_off, q->caps, q->ids, q->seqs};
+	RaggedTabs t = {q->desc, q->dst_off, q->caps, q->ids, q->seqs, q->checksums};
 	const bool rice = q->encoder_param && (q->encoder_param & (q->encoder_param - 1u)) == 0u;
 	ragged_encode(k, t, q->sample_bytes, q->preprocessing, q->encoder_type, rice, q->blocks, e->stream);
 	HIPCHECK(hipGetLastError());

@@ -106,7 +106,11 @@ void cmp_gpu_engine_destroy(struct cmp_gpu_engine *engine);
  *                               default, 256 MiB.
  *   CMP_GPU_OPT_IMAGE_RAGGED    (5, defined with cmp_gpu_compress_image) frames
  *                               of unequal sizes share one encode launch there;
- *                               0: off (the default). */
+ *                               0: off (the default).
+ *   CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM (6, defined with cmp_gpu_compress_image)
+ *                               1: checksum-enabled contexts take those launches
+ *                               too; 0: they do not (the default); any other
+ *                               value: CMP_ERR_PARAMS_INVALID. */
 #define CMP_GPU_OPT_EXCLUSIVE 1u
 #define CMP_GPU_OPT_WALK_SEGMENT 2u
 #define CMP_GPU_OPT_NO_CONTEXT_WALK 3u
@@ -368,9 +372,13 @@ uint64_t cmp_gpu_frame_table(const void *image, uint64_t size, uint64_t *offsets
  * CMP_GPU_OPT_IMAGE_RAGGED (engine option; 0, the default: off) changes only
  * how the call schedules this work; no result depends on its value.  It
  * applies when the context keeps no state in its work buffer (no MODEL pass,
- * no IWT), the checksum and the uncompressed fallback are disabled and
- * batch_flags is 0; any other call takes the runs above whatever the option
- * says.  The table is then cut into pieces.  A run of at least 2 frames whose
+ * no IWT), the checksum is disabled, or option 6 is 1, the uncompressed
+ * fallback is disabled and batch_flags is 0; any other call takes the runs
+ * above whatever the option says.  CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM (engine
+ * option; 0, the default, or 1) is that opt-in of checksum-enabled contexts:
+ * their ragged pieces take one XXH32 over all frames of the piece ahead of the
+ * encode launches, which append the four bytes.  It changes the schedule only
+ * as well.  The table is then cut into pieces.  A run of at least 2 frames whose
  * samples take at least the keep threshold (value 1: the built-in one, 1 MiB;
  * any other value: that many bytes) stays a run as above, and so do frames
  * that are refused.  Every other frame joins a ragged piece: consecutive
@@ -388,6 +396,7 @@ uint64_t cmp_gpu_frame_table(const void *image, uint64_t size, uint64_t *offsets
  * are valid after cmp_gpu_synchronize.  Build-defined extension.
  */
 #define CMP_GPU_OPT_IMAGE_RAGGED 5u /* cmp_gpu_engine_set_option: 0 off, 1 on, else on with that keep threshold in bytes */
+#define CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM 6u /* cmp_gpu_engine_set_option: 0 off, 1 checksum-enabled contexts take ragged pieces */
 #define CMP_GPU_IMG_SRC_BIG_ENDIAN 0x1u /* samples in src are big-endian 16-bit words (sample files) */
 
 struct cmp_gpu_encode_image {

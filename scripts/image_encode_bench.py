@@ -28,6 +28,13 @@ the run path against the same frames in a ragged piece (option value
 0xFFFFFFFF: no run is kept).  --once takes VARIANT names of that mode too.
 
     python scripts/image_encode_bench.py --ragged --out profiles/image_encode_ragged.json
+
+--checksum measures CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM the
+same way: the 1024 frames of 64 Ki + 2 i samples under a checksum-enabled
+context, CMP_GPU_OPT_IMAGE_RAGGED on throughout, option 6 off (the context is
+ineligible: 1024 runs with a checksum launch pair each) against option 6 on.
+
+    python scripts/image_encode_bench.py --checksum --out profiles/image_encode_ragged_checksum.json
 """
 import argparse
 import importlib.util
@@ -164,13 +171,102 @@ def ragged_main(a):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def checksum_main(a):
+    """Option 6 off against on under a checksum-enabled context (module docstring)."""
+    import torch
+    pkg = load_pkg()
+    api = pkg.cmpapi
+    lib = pkg.load()
+    assert lib.gpu_available(), "no HIP device"
+    eng = lib.engine()
+    ns = [N + 2 * i for i in range(FRAMES)]
+    stride = (2 * ns[-1] + 15) // 16 * 16  # bytes between frames: every frame 16-byte aligned
+    native = torch.empty(FRAMES * stride // 2 + 8, dtype=torch.int16, device="cuda")
+    assert eng.synthesize(native.data_ptr(), 2, 0xA1A5, 0, stride // 2, FRAMES, stride, 32) == 0
+    torch.cuda.synchronize()
+    host = native.cpu().numpy()[:FRAMES * stride // 2].view(np.uint16)
+    be = torch.from_numpy(host.byteswap().view(np.uint8).copy()).cuda()
+    offs = np.arange(FRAMES, dtype=np.uint64) * stride
+    fbs = np.array([2 * n for n in ns], dtype=np.uint32)
+    cap = lib.compress_bound(int(fbs[-1]))
+    out = torch.zeros(FRAMES * cap, dtype=torch.uint8, device="cuda")
+    ooffs = torch.zeros(FRAMES + 1, dtype=torch.int64, device="cuda")
+    sizes = torch.zeros(FRAMES, dtype=torch.int32, device="cuda")
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
+    prm = api.CmpParams(primary_preprocessing=1, primary_encoder_type=1, primary_encoder_param=G, checksum_enabled=1)
+    ctxs = pkg.context_array(1)
+    assert eng.set_option(pkg.OPT_IMAGE_RAGGED, 1) == 0
+
+    def image(src, flags, option6):
+        def call():
+            assert eng.set_option(pkg.OPT_IMAGE_RAGGED_CHECKSUM, option6) == 0
+            rc = eng.compress_image(ctxs[0], "u16", src.data_ptr(), src.numel() * src.element_size(), offs, fbs,
+                                    out.data_ptr(), FRAMES * cap, ooffs.data_ptr(), sizes.data_ptr(), 0, flags)
+            assert rc == 0, api.error_name(rc)
+        return call
+
+    calls = {"native_off": image(native, 0, 0), "native_on": image(native, 0, 1),
+             "be_off": image(be, pkg.IMG_SRC_BIG_ENDIAN, 0), "be_on": image(be, pkg.IMG_SRC_BIG_ENDIAN, 1)}
+    assert a.once is None or a.once in calls, a.once
+
+    def timed(fn):
+        assert not api.is_error(lib.initialise(ctxs[0], prm))
+        flush.fill_(1)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3  # us
+
+    # warm up, and the variants against each other: the same frames, checksums
+    # included, identifiers excepted (header bytes 8..13 come from the clock)
+    want, total = None, 0
+    for name, fn in calls.items():
+        for _ in range(2):
+            assert not api.is_error(lib.initialise(ctxs[0], prm))
+            fn()
+        assert eng.synchronize() == 0
+        b, o, sz = out.cpu().numpy(), ooffs.cpu().numpy(), sizes.cpu().numpy().astype(np.int64)
+        assert (sz > 0).all() and int(o[FRAMES]) == int(sz.sum())
+        got = [bytes(b[int(o[f]):int(o[f]) + 8]) + bytes(b[int(o[f]) + 14:int(o[f]) + int(sz[f])])
+               for f in range(FRAMES)]
+        assert all(g[15 - 6] & 8 for g in got), "checksum bit"
+        want, total = want or got, int(sz.sum())
+        assert got == want, f"{name} differs"
+    if a.once:
+        timed(calls[a.once])
+        return
+    res = {"workload": {"frames": FRAMES, "samples_per_frame": "65536 + 2 i", "preprocessing": "DIFF",
+                        "encoder": "GOLOMB_ZERO", "g": G, "checksum_enabled": 1, "image_ragged": 1,
+                        "sample_bytes": int(fbs.sum()), "compressed_bytes": total, "cold": True, "reps": a.reps}}
+    t = {name: [] for name in calls}
+    for _ in range(a.reps):
+        for name in calls:
+            t[name].append(timed(calls[name]))
+    for name in calls:
+        res[name + "_us"] = stats(t[name])
+    for kind in ("native", "be"):
+        off, on = res[kind + "_off_us"], res[kind + "_on_us"]
+        res[kind + "_off_over_on"] = off["median"] / on["median"]
+        res[kind + "_ranges_overlap"] = not (on["max"] < off["min"] or off["max"] < on["min"])
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--out")
     ap.add_argument("--ragged", action="store_true", help="the CMP_GPU_OPT_IMAGE_RAGGED measurements")
     ap.add_argument("--once", help="warm up, then one cold call of this variant (for a profiler)")
+    ap.add_argument("--checksum", action="store_true", help="the CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM measurements")
     a = ap.parse_args()
+    if a.checksum:
+        return checksum_main(a)
     if a.ragged:
         return ragged_main(a)
     assert a.once is None or a.once in VARIANTS, a.once
