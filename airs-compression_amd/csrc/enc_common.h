@@ -751,7 +751,8 @@ bool rice_encode(const KArgs &k, uint32_t pre, hipStream_t s, bool stream);
 bool rice_auto_encode(const KArgs &k, uint32_t pre, hipStream_t s);
 void stream_encode(const KArgs &k, uint32_t sample_bytes, uint32_t pre, uint32_t enc, bool rice, bool full,
 		   uint32_t grid, hipStream_t s);
-// the ragged encode kernel (enc_ragged.hip): frames of different sizes in one
+// ragged encode launches (enc_ragged.hip; encode_kernel's ragged mode, of which
+// this is the second kernel argument): frames of different sizes in one
 // launch.  Block b works on desc[b]; the other arrays are indexed by the
 // descriptor's frame (the frame's index in the piece).  Of KArgs it uses dst,
 // status, agg, tail, ticket, epoch, g, outlier_param and img_words.

@@ -1,10 +1,13 @@
 // enc_kernel.h -- the encode kernel template (encode_kernel), shared by
-// encode.hip (frame launches) and enc_stream.hip (payload-only streams), so
-// that its instantiations compile in separate translation units.  Reference
-// citations as in encode.hip.
+// encode.hip (frame launches), enc_stream.hip (payload-only streams) and
+// enc_ragged.hip (frames of different sizes in one launch), so that its
+// instantiations compile in separate translation units.  Reference citations
+// as in encode.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "enc_common.h"
 
@@ -17,6 +20,10 @@ namespace airs {
 //   ENC    UNCOMPRESSED / GOLOMB_ZERO / GOLOMB_MULTI
 //   RICE   Golomb parameter is a power of two (shift instead of divide)
 //   MODEL  0: no model, 1: store samples (primary pass), 2: update (secondary)
+//   Tabs   RaggedTabs: the ragged mode (enc_ragged.hip), frames
+//          of different sizes in one launch: a block takes its frame and segment
+//          from its descriptor t.desc[blockIdx.x], not from the grid, and the
+//          frame's fields from t's per-frame arrays.  NoTabs: every other launch
 //
 // One workgroup encodes one segment of SEG_CHUNKS(W, MODEL) chunks of 4096
 // samples; lane t owns samples [16t, 16t+16) of every chunk.  All chunk loads
@@ -61,9 +68,16 @@ __host__ __device__ constexpr uint32_t seg_images(int W, int MODEL)
 #endif
 #define AIRS_AUTO_ABL(b) ((AIRS_AUTO_ABLATE & (b)) != 0)
 
-template <int W, int PRE, int ENC, bool RICE, int MODEL, bool FULL, bool AUTO = false, bool STREAM = false>
-__global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
+struct NoTabs {}; // the second kernel argument of every launch without per-frame tables
+
+template <int W, int PRE, int ENC, bool RICE, int MODEL, bool FULL, bool AUTO = false, bool STREAM = false,
+	  typename Tabs = NoTabs>
+__global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a, Tabs t)
 {
+	constexpr bool RAGGED = std::is_same<Tabs, RaggedTabs>::value;
+	static_assert(RAGGED || std::is_same<Tabs, NoTabs>::value, "tables: RaggedTabs or none");
+	static_assert(!RAGGED || (MODEL == 0 && !FULL && !AUTO && !STREAM && (PRE == PRE_NONE || PRE == PRE_DIFF)),
+		      "ragged launches: NONE or DIFF, no model, no fused Rice selection, no stream");
 	// AUTO: the frame's k is chosen here from the samples already in registers
 	// (one read); the frame's segments meet once at the 16-candidate granules,
 	// which also give every segment its exclusive bit offset (no look-back)
@@ -104,9 +118,25 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 		return;
 	const uint32_t wid = __builtin_amdgcn_readfirstlane(tid >> 6); // wave-uniform
 
+	// ---- RAGGED: the block's descriptor (airs_ragged_desc) says what the other
+	// modes derive from the grid: one scalar load before the sample loads (glc:
+	// the host rewrites the table between launches).  The host orders the
+	// blocks by segment index, then frame: a frame's segments are dispatched in
+	// order, as below.  (The text below stays at function scope: nested in an
+	// else of the mode, it moved the AUTO instantiations' SGPR spills.)
+	typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+	u32x8 d = {};
+	if constexpr (RAGGED) {
+		const uint64_t *dp = lb_sptr(reinterpret_cast<const uint64_t *>(t.desc + blockIdx.x));
+		asm volatile("s_load_dwordx8 %0, %1, 0x0 glc\n\t"
+			     "s_waitcnt lgkmcnt(0)"
+			     : "=&s"(d)
+			     : "s"(dp)
+			     : "memory");
+	}
 	// ---- segment id: dispatch order (or an atomic ticket, debug switch) ----
 	uint32_t seg = blockIdx.x;
-	if (DBG(4u)) {
+	if (!RAGGED && DBG(4u)) {
 		if (tid == 0)
 			s_misc[0] = atomicAdd(a.ticket, 1u) - a.ticket_base;
 		__syncthreads();
@@ -121,9 +151,12 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 	// XCD: blocks b, b + 8, b + 16, ... share an XCD (MI355X_MICROARCH.md,
 	// dispatch), so frame 8 j + x takes blocks x + 8 (j spf + s), s < spf.
 	// The grid is padded to whole groups of 8 frames.
-	const uint32_t nfr = a.num_segs / a.segs_per_frame;
+	const uint32_t nfr = RAGGED ? 0u : a.num_segs / a.segs_per_frame;
 	uint32_t sif, lf;
-	if (AUTOK) {
+	if (RAGGED) {
+		sif = d[3];
+		lf = d[4]; // the frame's index in the piece
+	} else if (AUTOK) {
 		const uint32_t p = seg >> 3;
 		sif = p % a.segs_per_frame;
 		lf = 8u * (p / a.segs_per_frame) + (seg & 7u);
@@ -133,20 +166,23 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 		sif = seg / nfr;
 		lf = seg - sif * nfr;
 	}
-	const uint32_t gseg = lf * a.segs_per_frame + sif; // granule slot: frame-major
+	const uint32_t gseg = (RAGGED ? d[5] : lf * a.segs_per_frame) + sif; // granule slot: frame-major
 	const uint32_t frame =
-		__builtin_amdgcn_readfirstlane(a.frame_list ? a.frame_list[lf] : a.frame_add + lf * a.frame_mul);
+		RAGGED ? lf
+		       : __builtin_amdgcn_readfirstlane(a.frame_list ? a.frame_list[lf] : a.frame_add + lf * a.frame_mul);
 	// a hole in a device-planned launch list (batch fallback path: the
 	// context takes the other pass this step, or none): the whole frame is
 	// skipped, and no segment of another frame waits on it
-	if (frame == AIRS_NO_FRAME)
+	if (!RAGGED && frame == AIRS_NO_FRAME)
 		return;
 	const bool is_first = sif == 0u;
-	const bool is_last = sif + 1u == a.segs_per_frame;
-	const uint32_t n = a.n;
+	// (RAGGED: the frame's last segment may hold any number of samples, down to one)
+	const bool is_last = RAGGED ? (uint64_t)(sif + 1u) * SEGN >= d[2] : sif + 1u == a.segs_per_frame;
+	const uint32_t n = RAGGED ? d[2] : a.n;
 	dbg_stamp(a, gseg, 0);
 
-	const uint8_t *fsrc = a.src + (uint64_t)frame * a.src_stride;
+	const uint8_t *fsrc = RAGGED ? reinterpret_cast<const uint8_t *>((uintptr_t)(((uint64_t)d[1] << 32) | d[0]))
+				     : a.src + (uint64_t)frame * a.src_stride;
 	// PRE_IWT: the residuals are the frame's IWT coefficients, computed into
 	// the work buffer by iwt_frame_kernel (reference preprocess.c:321-353);
 	// the samples themselves are only needed to store the model (MODEL == 1)
@@ -194,6 +230,13 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 			prevld[c] = W == 2 ? (uint32_t)reinterpret_cast<const uint16_t *>(fsrc)[firstc[c] - 1u]
 					   : reinterpret_cast<const uint32_t *>(fsrc)[firstc[c] - 1u] & 0xFFFFu;
 	}
+	// RAGGED: the frame's destination and capacity, while the samples are in flight
+	uint8_t *rag_dst = nullptr;
+	uint32_t rag_cap = 0u;
+	if constexpr (RAGGED) {
+		rag_dst = a.dst + t.dst_off[frame];
+		rag_cap = __builtin_amdgcn_readfirstlane(t.caps[frame]);
+	}
 
 	// zero both LDS chunk images while the loads are in flight
 	{
@@ -204,7 +247,8 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 	}
 
 	// (AUTO: set once the frame's k is known, after the residuals)
-	uint32_t gpar = AUTOK ? 1u : __builtin_amdgcn_readfirstlane(a.frame_g ? a.frame_g[frame] : a.g);
+	// (RAGGED: one coder parameter for the launch, no frame_g)
+	uint32_t gpar = AUTOK ? 1u : __builtin_amdgcn_readfirstlane(!RAGGED && a.frame_g ? a.frame_g[frame] : a.g);
 	Coder cd = make_coder<ENC>(ENC == ENC_RAW ? 1u : gpar, a.outlier_param);
 
 	// ---- phase 1: residuals, mapped values, code lengths ------------------
@@ -639,8 +683,8 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 	for (uint32_t c = 0; c < CH; c++)
 		last_ne = tot[c] ? c : last_ne;
 
-	uint8_t *fdst = a.dst + (uint64_t)frame * a.dst_stride;
-	const uint32_t cap = a.cap;
+	uint8_t *fdst = RAGGED ? rag_dst : a.dst + (uint64_t)frame * a.dst_stride;
+	const uint32_t cap = RAGGED ? rag_cap : a.cap;
 	const __amdgpu_buffer_rsrc_t dst_rsrc = __builtin_amdgcn_make_buffer_rsrc(fdst, 0, (int)(cap & ~3u), 0x00020000);
 	uint32_t P = 0u;
 	uint32_t pred_c = 0u; // (lane 0 of wave 0) bits preceding chunk c in its first dword
@@ -942,18 +986,32 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 	if (!STREAM && is_last && tid == 0) {
 		const uint32_t endbit = P + A;
 		const uint32_t payload_bytes = (endbit + 7u) >> 3;
-		const uint32_t size = payload_bytes + (a.checksum ? 4u : 0u);
-		if (a.checksum) {
-			const uint32_t ck = a.checksums[frame];
+		// (RAGGED: checksums, identifiers and sequence numbers per frame of the
+		// piece; a launch has checksums when it has their array)
+		const uint32_t *cks = a.checksums;
+		bool has_ck = a.checksum;
+		if constexpr (RAGGED) {
+			cks = t.checksums;
+			has_ck = cks != nullptr;
+		}
+		const uint32_t size = payload_bytes + (has_ck ? 4u : 0u);
+		if (has_ck) {
+			const uint32_t ck = cks[frame];
 			for (uint32_t b = 0; b < 4u; b++)
 				if (payload_bytes + b < cap)
 					fdst[payload_bytes + b] = (uint8_t)(ck >> (24u - 8u * b));
 		}
-		const uint64_t id = a.ids ? a.ids[lf] : a.id_base + (uint64_t)lf * a.id_step;
+		const uint64_t *ids = a.ids;
+		const uint8_t *seqs = a.seqs;
+		if constexpr (RAGGED) {
+			ids = t.ids;
+			seqs = t.seqs;
+		}
+		const uint64_t id = RAGGED || ids ? ids[lf] : a.id_base + (uint64_t)lf * a.id_step;
+		const uint32_t seq = RAGGED || seqs ? seqs[frame] : a.seq;
 		uint32_t h[5];
-		header_words(h, size, 2u * n, id, a.seqs ? a.seqs[frame] : a.seq, PRE, a.checksum ? 1u : 0u, ENC,
-			     PRE == PRE_MODEL ? a.model_rate : 0u, ENC == ENC_RAW ? 0u : gpar,
-			     ENC == ENC_RAW ? 0u : cd.outlier);
+		header_words(h, size, 2u * n, id, seq, PRE, has_ck ? 1u : 0u, ENC, PRE == PRE_MODEL ? a.model_rate : 0u,
+			     ENC == ENC_RAW ? 0u : gpar, ENC == ENC_RAW ? 0u : cd.outlier);
 		const uint32_t hwords = EXT_HDR ? 5u : 4u;
 		if (((uintptr_t)fdst & 7u) == 0u && cap >= 4u * hwords) {
 			// three stores instead of five (8-byte aligned frame): the partial
@@ -976,7 +1034,7 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 		else if (size > 0xFFFFFFu)
 			st = ERRV(E_HDR_CMP_SIZE_TOO_LARGE);
 		a.status[frame] = st;
-		if (a.needed)
+		if (!RAGGED && a.needed)
 			a.needed[frame] = size;
 	}
 }
@@ -984,11 +1042,45 @@ __global__ __launch_bounds__(EWG) AIRS_EWPE_ATTR void encode_kernel(KArgs a)
 // Launch an encode kernel over `grid` blocks (segments).  (A persistent form,
 // co-resident workgroups walking the segments, was measured slower: DESIGN.md
 // 5.2; passing the kernel arguments on to a device function by reference also
-// cost 20 %: the compiler kept them in spilled SGPRs, read back by v_readlane.)
-template <typename Kern>
-static inline void launch_segments(Kern kern, const KArgs &k, uint32_t grid, size_t lds, hipStream_t s)
+// cost 20 %: the compiler kept them in spilled SGPRs, read back by v_readlane.
+// The kernel's body in a __forceinline__ function of (const KArgs &), shared
+// with a ragged kernel, moved the register allocation of 22 of the 40 stream
+// instantiations, by up to 17 VGPRs; so the ragged geometry is a mode of the
+// kernel itself: DESIGN.md 3.4.5.)  `t`: the ragged launch's tables, or none.
+template <typename Kern, typename Tabs = NoTabs>
+static inline void launch_segments(Kern kern, const KArgs &k, uint32_t grid, size_t lds, hipStream_t s,
+				   const Tabs &t = Tabs())
 {
-	hipLaunchKernelGGL(kern, dim3(grid), dim3(EWG), lds, s, k);
+	hipLaunchKernelGGL(kern, dim3(grid), dim3(EWG), lds, s, k, t);
+}
+
+template <int V>
+using ic = std::integral_constant<int, V>;
+
+// f(enc, rice) for the coder of a launch, as std::integral_constants: the five
+// coder forms the kernel is instantiated for (UNCOMPRESSED has one)
+template <typename F>
+static inline void with_coder(uint32_t enc, bool rice, F f)
+{
+	if (enc == ENC_RAW)
+		f(ic<ENC_RAW>(), std::true_type());
+	else if (enc == ENC_ZERO)
+		rice ? f(ic<ENC_ZERO>(), std::true_type()) : f(ic<ENC_ZERO>(), std::false_type());
+	else
+		rice ? f(ic<ENC_MULTI>(), std::true_type()) : f(ic<ENC_MULTI>(), std::false_type());
+}
+
+// f(w, pre, enc, rice) for stream and ragged launches: samples of 2 or 4
+// bytes, NONE or DIFF, and the coder
+template <typename F>
+static inline void with_width_pre_coder(uint32_t sample_bytes, uint32_t pre, uint32_t enc, bool rice, F f)
+{
+	with_coder(enc, rice, [&](auto e, auto r) {
+		if (sample_bytes == 2)
+			pre == PRE_DIFF ? f(ic<2>(), ic<PRE_DIFF>(), e, r) : f(ic<2>(), ic<PRE_NONE>(), e, r);
+		else
+			pre == PRE_DIFF ? f(ic<4>(), ic<PRE_DIFF>(), e, r) : f(ic<4>(), ic<PRE_NONE>(), e, r);
+	});
 }
 
 } // namespace airs

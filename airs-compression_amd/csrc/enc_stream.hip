@@ -15,38 +15,6 @@
 
 namespace airs {
 
-template <int W, int PRE, int ENC, bool RICE>
-static void stream_go(const KArgs &k, bool full, uint32_t grid, hipStream_t s)
-{
-	const size_t lds = (size_t)seg_images(W, 0) * (k.img_words + 4u) * 4u;
-	if (full)
-		launch_segments(encode_kernel<W, PRE, ENC, RICE, 0, true, false, true>, k, grid, lds, s);
-	else
-		launch_segments(encode_kernel<W, PRE, ENC, RICE, 0, false, false, true>, k, grid, lds, s);
-}
-
-template <int W, int PRE>
-static void stream_enc(const KArgs &k, uint32_t enc, bool rice, bool full, uint32_t grid, hipStream_t s)
-{
-	switch (enc) {
-	case ENC_RAW:
-		stream_go<W, PRE, ENC_RAW, true>(k, full, grid, s);
-		break;
-	case ENC_ZERO:
-		if (rice)
-			stream_go<W, PRE, ENC_ZERO, true>(k, full, grid, s);
-		else
-			stream_go<W, PRE, ENC_ZERO, false>(k, full, grid, s);
-		break;
-	default:
-		if (rice)
-			stream_go<W, PRE, ENC_MULTI, true>(k, full, grid, s);
-		else
-			stream_go<W, PRE, ENC_MULTI, false>(k, full, grid, s);
-		break;
-	}
-}
-
 uint32_t stream_segn(uint32_t sample_bytes)
 {
 	return seg_chunks(sample_bytes == 4 ? 4 : 2, 0) * AIRS_SEG;
@@ -55,17 +23,15 @@ uint32_t stream_segn(uint32_t sample_bytes)
 void stream_encode(const KArgs &k, uint32_t sample_bytes, uint32_t pre, uint32_t enc, bool rice, bool full,
 		   uint32_t grid, hipStream_t s)
 {
-	if (sample_bytes == 2) {
-		if (pre == PRE_DIFF)
-			stream_enc<2, PRE_DIFF>(k, enc, rice, full, grid, s);
+	with_width_pre_coder(sample_bytes, pre, enc, rice, [&](auto w, auto p, auto e, auto r) {
+		constexpr int W = w, PRE = p, ENC = e;
+		constexpr bool RICE = r;
+		const size_t lds = (size_t)seg_images(W, 0) * (k.img_words + 4u) * 4u;
+		if (full)
+			launch_segments(encode_kernel<W, PRE, ENC, RICE, 0, true, false, true>, k, grid, lds, s);
 		else
-			stream_enc<2, PRE_NONE>(k, enc, rice, full, grid, s);
-	} else {
-		if (pre == PRE_DIFF)
-			stream_enc<4, PRE_DIFF>(k, enc, rice, full, grid, s);
-		else
-			stream_enc<4, PRE_NONE>(k, enc, rice, full, grid, s);
-	}
+			launch_segments(encode_kernel<W, PRE, ENC, RICE, 0, false, false, true>, k, grid, lds, s);
+	});
 }
 
 } // namespace airs

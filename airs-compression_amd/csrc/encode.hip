@@ -1529,23 +1529,11 @@ static void launch_encode(const KArgs &k, bool full, uint32_t grid, hipStream_t 
 template <int W, int PRE, int MODEL>
 static void dispatch_enc(const KArgs &k, uint32_t enc, bool rice, bool full, uint32_t grid, hipStream_t s)
 {
-	switch (enc) {
-	case ENC_RAW:
-		launch_encode<W, PRE, ENC_RAW, true, MODEL>(k, full, grid, s);
-		break;
-	case ENC_ZERO:
-		if (rice)
-			launch_encode<W, PRE, ENC_ZERO, true, MODEL>(k, full, grid, s);
-		else
-			launch_encode<W, PRE, ENC_ZERO, false, MODEL>(k, full, grid, s);
-		break;
-	default:
-		if (rice)
-			launch_encode<W, PRE, ENC_MULTI, true, MODEL>(k, full, grid, s);
-		else
-			launch_encode<W, PRE, ENC_MULTI, false, MODEL>(k, full, grid, s);
-		break;
-	}
+	with_coder(enc, rice, [&](auto e, auto r) {
+		constexpr int ENC = e;
+		constexpr bool RICE = r;
+		launch_encode<W, PRE, ENC, RICE, MODEL>(k, full, grid, s);
+	});
 }
 
 template <int W>

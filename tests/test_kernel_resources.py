@@ -38,11 +38,20 @@ BUDGETS = {
     # kernel does not take (k > 7, holes in device-planned launch lists); no
     # longer a bench path, so the kernel-argument padding that kept it at 13
     # spills went (round 5: the Rice kernels went from 8 spills to 0)
-    "_ZN4airs13encode_kernelILi2ELi1ELi1ELb1ELi0ELb1ELb0ELb0EEEvNS_5KArgsE": (128, 40),
+    "_ZN4airs13encode_kernelILi2ELi1ELi1ELb1ELi0ELb1ELb0ELb0ENS_6NoTabsEEEvNS_5KArgsET7_": (128, 40),
     # cfg3: encode_kernel's fused per-frame Rice selection
-    "_ZN4airs13encode_kernelILi2ELi1ELi1ELb1ELi0ELb1ELb1ELb0EEEvNS_5KArgsE": (128, 0),
+    "_ZN4airs13encode_kernelILi2ELi1ELi1ELb1ELi0ELb1ELb1ELb0ENS_6NoTabsEEEvNS_5KArgsET7_": (128, 0),
     # cfg2s: payload-only stream
-    "_ZN4airs13encode_kernelILi2ELi1ELi1ELb1ELi0ELb1ELb0ELb1EEEvNS_5KArgsE": (128, 0),
+    "_ZN4airs13encode_kernelILi2ELi1ELi1ELb1ELi0ELb1ELb0ELb1ENS_6NoTabsEEEvNS_5KArgsET7_": (128, 0),
+    # ragged launches (encode_kernel's ragged mode), Rice/ZERO,
+    # the instantiations the image encoder's measurements run on: u16 NONE and
+    # DIFF (4 waves per SIMD: <= 128 VGPRs), i16-in-i32 NONE and DIFF (6: <= 80).
+    # The spill budgets are the counts of the separate ragged kernel this mode
+    # replaced (12, 12, 0, 0)
+    "_ZN4airs13encode_kernelILi2ELi0ELi1ELb1ELi0ELb0ELb0ELb0ENS_10RaggedTabsEEEvNS_5KArgsET7_": (128, 12),
+    "_ZN4airs13encode_kernelILi2ELi1ELi1ELb1ELi0ELb0ELb0ELb0ENS_10RaggedTabsEEEvNS_5KArgsET7_": (128, 12),
+    "_ZN4airs13encode_kernelILi4ELi0ELi1ELb1ELi0ELb0ELb0ELb0ENS_10RaggedTabsEEEvNS_5KArgsET7_": (80, 0),
+    "_ZN4airs13encode_kernelILi4ELi1ELi1ELb1ELi0ELb0ELb0ELb0ENS_10RaggedTabsEEEvNS_5KArgsET7_": (80, 0),
     # cfg5 / cfg5fb: the context walk (1024-thread workgroups: <= 128 VGPRs)
     "_ZN4airs15walk_ctx_kernelILi4ELi1ELi1ELb1ELi2ELb1ELi4EEEvNS_5WArgsE": (128, 74),
     # the segment walk, 16 samples per lane and 8 (cfg5s8: grids of fewer than 1024 4096-sample workgroups)
