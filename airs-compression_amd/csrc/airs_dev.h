@@ -434,7 +434,7 @@ enum airs_ragged_stat {
 uint32_t airs_dev_ragged_stats(uint64_t *out, uint32_t n);
 
 /* XXH32 (seed 419764627) over frames of different sizes that lie anywhere
- * (ck_ragged.hip): out[j] is what airs_dev_checksum gives for
+ * (checksum.hip): out[j] is what airs_dev_checksum gives for
  * the n[j] samples at src[j], as big-endian 16-bit words (of 4-byte samples the
  * low halves).  A product kernel writes frame j's stripes x P2 to the engine's
  * checksum-products scratch at byte off[j]; a chain kernel, four lanes per

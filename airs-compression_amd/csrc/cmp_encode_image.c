@@ -15,7 +15,7 @@
  * joins a ragged piece, which is one ingest, one encode launch per pass
  * (enc_ragged.hip), one scan and one emit.  With
  * CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM a checksum-enabled context takes the
- * pieces too: one ragged XXH32 per piece (ck_ragged.hip) ahead of its encode
+ * pieces too: one ragged XXH32 per piece (checksum.hip) ahead of its encode
  * launches, which append the four bytes.
  */
 #include <stdint.h>

@@ -274,6 +274,14 @@ __device__ __forceinline__ void gran_store(uint64_t *p, uint64_t v)
 	__hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// sample i of the frame at f (W = bytes per sample; the low 16 bits count)
+template <int W>
+__device__ __forceinline__ uint32_t sample_at(const uint8_t *f, uint32_t i)
+{
+	return W == 2 ? (uint32_t)reinterpret_cast<const uint16_t *>(f)[i]
+		      : reinterpret_cast<const uint32_t *>(f)[i] & 0xFFFFu;
+}
+
 // 16 samples of this lane: first sample index `first` inside the frame
 // (vector loads when the frame base is 16-byte aligned: uniform per frame)
 template <int W>
@@ -770,5 +778,8 @@ void ragged_encode(const KArgs &k, const RaggedTabs &t, uint32_t sample_bytes, u
 // host-side launch counters (airs_dev_launch_stats, airs_dev.h), one increment
 // at each launch site
 void launch_count(uint32_t which);
+// a failed HIP call: its text for airs_dev_last_error (and stderr); returns
+// ERRV(E_GENERIC)
+uint32_t hip_fail(hipError_t e, const char *what);
 
 } // namespace airs

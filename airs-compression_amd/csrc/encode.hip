@@ -438,179 +438,6 @@ __global__ __launch_bounds__(256) void iwt_level_kernel(IwtArgs a, uint32_t s, u
 }
 
 // ---------------------------------------------------------------------
-// XXH32 per frame over big-endian 16-bit samples (reference header.c:137-163).
-// The four accumulators of a frame run in four lanes; each stripe is 8
-// samples = 16 bytes, lane q consumes bytes 4q..4q+3 of every stripe.
-// ---------------------------------------------------------------------
-#define XP1 2654435761u
-#define XP2 2246822519u
-#define XP3 3266489917u
-#define XP4 668265263u
-#define XP5 374761393u
-
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, uint32_t r)
-{
-	return (x << r) | (x >> (32u - r));
-}
-
-template <int W>
-__device__ __forceinline__ uint32_t sample_at(const uint8_t *f, uint32_t i)
-{
-	return W == 2 ? (uint32_t)reinterpret_cast<const uint16_t *>(f)[i]
-		      : reinterpret_cast<const uint32_t *>(f)[i] & 0xFFFFu;
-}
-
-// little-endian read of the BE byte image: bytes (hi0, lo0, hi1, lo1)
-__device__ __forceinline__ uint32_t be_pair(uint32_t s0, uint32_t s1)
-{
-	return ((s0 >> 8) & 0xFFu) | ((s0 & 0xFFu) << 8) | (((s1 >> 8) & 0xFFu) << 16) | ((s1 & 0xFFu) << 24);
-}
-
-// one XXH32 round with the input's P2 product already formed: add, rotate,
-// multiply as three dependent instructions (the compiler would fuse the add
-// into a 64-bit v_mad_u64_u32, whose latency is longer)
-__device__ __forceinline__ uint32_t xxh_round_pre(uint32_t acc, uint32_t yp2)
-{
-	asm volatile("v_add_u32 %0, %0, %1\n\tv_alignbit_b32 %0, %0, %0, 19\n\tv_mul_lo_u32 %0, %0, %2"
-		     : "+v"(acc)
-		     : "v"(yp2), "s"(XP1));
-	return acc;
-}
-
-// XXH32 in two launches (the default): ck_pre_kernel forms every stripe's
-// four inputs x P2 (the big-endian words of the samples, multiplied off the
-// chain) into a scratch buffer with all the parallelism of the frame;
-// ck_chain_kernel then runs only the 64 serial chains of 16 frames per wave,
-// reading its inputs 128 rounds ahead.  Y is laid out for the chain wave:
-// per group of 16 frames, for every 4 rounds, 64 chains x 16 bytes
-// (chain = 4 (frame % 16) + accumulator), so one 16-byte load per lane reads
-// 1 KiB contiguous.  S4 = stripes rounded up to 4.
-// VN: frames of different sizes in one launch (the decoder's verification):
-// frame f has frame_n[f] samples (0: none, nothing is written for it), n is
-// the largest of them and sizes Y.
-template <int W, bool VN>
-__global__ __launch_bounds__(256) void ck_pre_kernel(const uint8_t *src, uint64_t stride, uint32_t n,
-						     uint32_t num_frames, const uint32_t *frame_list, uint32_t S4,
-						     uint32_t *Y, const uint32_t *frame_n)
-{
-	// a workgroup covers 16 frames x 16 round quads, frame fastest: the 64
-	// lanes of a wave write 4 KiB of Y contiguous (their four stores fill it)
-	const uint32_t lf = blockIdx.x * 16u + (threadIdx.x & 15u);
-	if (lf >= num_frames)
-		return;
-	const uint32_t frame = frame_list ? frame_list[lf] : lf;
-	const uint32_t stripes = (VN ? frame_n[frame] : n) / 8u;
-	const uint8_t *f = src + (uint64_t)frame * stride;
-	// rounds 4 r4 .. 4 r4 + 3 (grid-stride: gridDim.y is capped)
-	for (uint32_t r4 = blockIdx.y * 16u + (threadIdx.x >> 4); 4u * r4 < stripes; r4 += gridDim.y * 16u) {
-		uint32_t y[4][4]; // [round][accumulator]
-		if (4u * r4 + 4u <= stripes && ((uintptr_t)f & 15u) == 0u) {
-#pragma unroll
-			for (uint32_t t = 0; t < 4u; t++) {
-				const uint32_t r = 4u * r4 + t;
-				if (W == 2) {
-					const uint4 v = reinterpret_cast<const uint4 *>(f)[r];
-					y[t][0] = __builtin_amdgcn_perm(v.x, v.x, 0x02030001u);
-					y[t][1] = __builtin_amdgcn_perm(v.y, v.y, 0x02030001u);
-					y[t][2] = __builtin_amdgcn_perm(v.z, v.z, 0x02030001u);
-					y[t][3] = __builtin_amdgcn_perm(v.w, v.w, 0x02030001u);
-				} else {
-					const uint4 a = reinterpret_cast<const uint4 *>(f)[2u * r];
-					const uint4 b = reinterpret_cast<const uint4 *>(f)[2u * r + 1u];
-					y[t][0] = be_pair(a.x & 0xFFFFu, a.y & 0xFFFFu);
-					y[t][1] = be_pair(a.z & 0xFFFFu, a.w & 0xFFFFu);
-					y[t][2] = be_pair(b.x & 0xFFFFu, b.y & 0xFFFFu);
-					y[t][3] = be_pair(b.z & 0xFFFFu, b.w & 0xFFFFu);
-				}
-			}
-		} else {
-#pragma unroll
-			for (uint32_t t = 0; t < 4u; t++) {
-				const uint32_t r = 4u * r4 + t;
-#pragma unroll
-				for (uint32_t q = 0; q < 4u; q++)
-					y[t][q] = r < stripes ? be_pair(sample_at<W>(f, 8u * r + 2u * q),
-								     sample_at<W>(f, 8u * r + 2u * q + 1u))
-							   : 0u;
-			}
-		}
-		uint4 *G = reinterpret_cast<uint4 *>(Y + (uint64_t)(lf >> 4) * 64u * S4) + (uint64_t)r4 * 64u + (lf & 15u) * 4u;
-#pragma unroll
-		for (uint32_t q = 0; q < 4u; q++)
-			G[q] = make_uint4(y[0][q] * XP2, y[1][q] * XP2, y[2][q] * XP2, y[3][q] * XP2);
-	}
-}
-
-template <int W, bool VN>
-__global__ __launch_bounds__(64) void ck_chain_kernel(const uint8_t *src, uint64_t stride, uint32_t n0,
-						      uint32_t num_frames, const uint32_t *frame_list, uint32_t S4,
-						      const uint32_t *Y, uint32_t *out, const uint32_t *frame_n)
-{
-	const uint32_t lane = threadIdx.x, q = lane & 3u;
-	const uint32_t lf = blockIdx.x * 16u + (lane >> 2);
-	const uint32_t n = !VN ? n0 : lf < num_frames ? frame_n[frame_list ? frame_list[lf] : lf] : 0u;
-	const bool valid = lf < num_frames && n;
-	const uint32_t len = 2u * n;
-	const uint32_t stripes = len >= 16u ? n / 8u : 0u;
-	const uint32_t seed = 419764627u;
-	uint32_t acc = q == 0 ? seed + XP1 + XP2 : q == 1 ? seed + XP2 : q == 2 ? seed : seed - XP1;
-	// this lane's chain: 16 bytes (4 rounds) every 1 KiB of its group
-	const uint4 *P = reinterpret_cast<const uint4 *>(Y + (uint64_t)blockIdx.x * 64u * S4) + lane;
-	// batches of 128 rounds (32 x 16 bytes per lane), the next batch loading
-	// while this one runs
-	constexpr uint32_t B = 32u;
-	const uint32_t nb = stripes / (4u * B);
-	uint4 cur[B], nxt[B];
-	if (nb) {
-#pragma unroll
-		for (uint32_t u = 0; u < B; u++)
-			cur[u] = P[64u * u];
-	}
-	for (uint32_t b = 0; b < nb; b++) {
-		const uint32_t nbase = (b + 1u < nb ? b + 1u : b) * B;
-#pragma unroll
-		for (uint32_t u = 0; u < B; u++)
-			nxt[u] = P[64u * (nbase + u)];
-#pragma unroll
-		for (uint32_t u = 0; u < B; u++) {
-			acc = xxh_round_pre(acc, cur[u].x);
-			acc = xxh_round_pre(acc, cur[u].y);
-			acc = xxh_round_pre(acc, cur[u].z);
-			acc = xxh_round_pre(acc, cur[u].w);
-		}
-#pragma unroll
-		for (uint32_t u = 0; u < B; u++)
-			cur[u] = nxt[u];
-	}
-	for (uint32_t r = nb * 4u * B; r < stripes; r++)
-		acc = xxh_round_pre(acc, reinterpret_cast<const uint32_t *>(P + 64u * (r >> 2))[r & 3u]);
-	const uint32_t a1 = __shfl_down(acc, 1, 4), a2 = __shfl_down(acc, 2, 4), a3 = __shfl_down(acc, 3, 4);
-	if (q != 0 || !valid)
-		return;
-	const uint32_t frame = frame_list ? frame_list[lf] : lf;
-	const uint8_t *f = src + (uint64_t)frame * stride;
-	uint32_t h = stripes ? rotl32(acc, 1) + rotl32(a1, 7) + rotl32(a2, 12) + rotl32(a3, 18) : seed + XP5;
-	h += len;
-	uint32_t i = 8u * stripes;
-	const uint32_t rem_bytes = len - 16u * stripes;
-	uint32_t bb = 0;
-	for (; bb + 4u <= rem_bytes; bb += 4u, i += 2u)
-		h = rotl32(h + be_pair(sample_at<W>(f, i), sample_at<W>(f, i + 1u)) * XP3, 17) * XP4;
-	if (bb < rem_bytes) {
-		const uint32_t s0 = sample_at<W>(f, i);
-		h = rotl32(h + ((s0 >> 8) & 0xFFu) * XP5, 11) * XP1;
-		h = rotl32(h + (s0 & 0xFFu) * XP5, 11) * XP1;
-	}
-	h ^= h >> 15;
-	h *= XP2;
-	h ^= h >> 13;
-	h *= XP3;
-	h ^= h >> 16;
-	out[frame] = h;
-}
-
-
-// ---------------------------------------------------------------------
 // Per-frame Rice parameter selection (build-defined rule; oracle
 // orc_select_rice_k): total_k = n(k+1) + sum_i min(v_i >> k, 16), v = m + 1.
 // The 129-bin histogram of enc_common.h (auto_term) is a sufficient statistic.
@@ -1181,12 +1008,15 @@ extern "C" uint32_t airs_dev_launch_stats(uint64_t *out, uint32_t n)
 	return m; // a caller that knows fewer counters gets the ones it knows
 }
 
-static uint32_t hip_fail(hipError_t e, const char *what)
+namespace airs
+{
+uint32_t hip_fail(hipError_t e, const char *what)
 {
 	snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
 	fprintf(stderr, "airscmp: %s\n", g_err);
 	return ERRV(E_GENERIC);
 }
+} // namespace airs
 
 #define HIPCHECK(x)                                 \
 	do {                                        \
@@ -2096,59 +1926,6 @@ extern "C" uint32_t airs_dev_encode_stream(struct airs_dev_engine *e, const void
 	launch_count(AIRS_STAT_ENCODE_STREAM);
 	HIPCHECK(hipGetLastError());
 	return 0;
-}
-
-template <bool VN>
-static uint32_t checksum_launch(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
-				uint32_t sample_bytes, uint32_t n, uint32_t num_frames, const uint32_t *frame_list,
-				uint32_t *out, const uint32_t *frame_n)
-{
-	if (!e || !n || !num_frames)
-		return ERRV(E_GENERIC);
-	dim3 grid((num_frames + 15) / 16);
-	// two launches: ck_pre_kernel forms the stripes' x P2
-	// products, ck_chain_kernel runs the serial accumulator chains
-	const uint32_t stripes = 2u * n >= 16u ? n / 8u : 0u;
-	const uint32_t S4 = (stripes + 3u) & ~3u;
-	// whole groups of 16 frames x 4 chains
-	// (at least one granule: frames under 8 samples have no stripes, and an
-	// empty request would return a slot that was never allocated)
-	uint32_t *Y = (uint32_t *)airs_dev_scratch(e, AIRS_NSLOT - 4, (size_t)grid.x * 64u * S4 * 4u + 16u);
-	if (!Y)
-		return ERRV(E_GENERIC);
-	if (stripes) {
-		const dim3 pg(grid.x, min((S4 / 4u + 15u) / 16u, 65535u));
-		if (sample_bytes == 2)
-			hipLaunchKernelGGL((ck_pre_kernel<2, VN>), pg, dim3(256), 0, e->stream, (const uint8_t *)src,
-					   src_stride, n, num_frames, frame_list, S4, Y, frame_n);
-		else
-			hipLaunchKernelGGL((ck_pre_kernel<4, VN>), pg, dim3(256), 0, e->stream, (const uint8_t *)src,
-					   src_stride, n, num_frames, frame_list, S4, Y, frame_n);
-	}
-	if (sample_bytes == 2)
-		hipLaunchKernelGGL((ck_chain_kernel<2, VN>), grid, dim3(64), 0, e->stream, (const uint8_t *)src,
-				   src_stride, n, num_frames, frame_list, S4, (const uint32_t *)Y, out, frame_n);
-	else
-		hipLaunchKernelGGL((ck_chain_kernel<4, VN>), grid, dim3(64), 0, e->stream, (const uint8_t *)src,
-				   src_stride, n, num_frames, frame_list, S4, (const uint32_t *)Y, out, frame_n);
-	HIPCHECK(hipGetLastError());
-	return 0;
-}
-
-extern "C" uint32_t airs_dev_checksum(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
-				      uint32_t sample_bytes, uint32_t n, uint32_t num_frames,
-				      const uint32_t *frame_list, uint32_t *out)
-{
-	return checksum_launch<false>(e, src, src_stride, sample_bytes, n, num_frames, frame_list, out, nullptr);
-}
-
-extern "C" uint32_t airs_dev_checksum_n(struct airs_dev_engine *e, const void *src, uint64_t src_stride,
-					uint32_t sample_bytes, uint32_t n_max, const uint32_t *frame_n,
-					uint32_t num_frames, uint32_t *out)
-{
-	if (!frame_n)
-		return ERRV(E_GENERIC);
-	return checksum_launch<true>(e, src, src_stride, sample_bytes, n_max, num_frames, nullptr, out, frame_n);
 }
 
 // the sliced selection over frame f at src + (f / div) * stride, or ptrs[j]

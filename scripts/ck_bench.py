@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Checksum-enabled encode: a bench workload with
-checksum_enabled=1, timed per call with HIP events (AIRS_CK_ALG=1|2 selects
-the single-wave or the producer/consumer checksum kernel for comparison).  usage: ck_bench.py cfg2|cfg4
+checksum_enabled=1, timed per call with HIP events.  usage: ck_bench.py cfg2|cfg4
 
 ck_bench.py ragged [OUT.json]: the ragged XXH32 (airs_dev_checksum_ragged,
 DESIGN.md 3.4.6) against airs_dev_checksum on the same 1024 equal frames of
@@ -127,5 +126,5 @@ for k in range(5):
 e1.record(stream)
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 5
-print(json.dumps(dict(workload=name, checksum=True, alg=os.environ.get("AIRS_CK_ALG", "0"),
-                      ms_per_call=round(ms, 4), GBps=round(nf * 2 * n / (ms * 1e-3) / 1e9, 1))))
+print(json.dumps(dict(workload=name, checksum=True, ms_per_call=round(ms, 4),
+                      GBps=round(nf * 2 * n / (ms * 1e-3) / 1e9, 1))))

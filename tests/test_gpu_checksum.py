@@ -27,7 +27,12 @@ def eng(prod):
     ("u16", 1, 3, 0), ("u16", 7, 5, 0), ("u16", 8, 17, 0), ("u16", 2048, 16, 0), ("u16", 2048 * 3 + 5, 33, 0),
     ("u16", 65536, 20, 0), ("u16", 1 << 20, 2, 0), ("u16", 5000, 9, 2), ("u16", 4099, 18, 6),
     ("i16_in_i32", 9, 4, 0), ("i16_in_i32", 2048 * 2 + 3, 17, 0), ("i16_in_i32", 70001, 5, 0),
-    ("i16_in_i32", 3001, 6, 4)])
+    ("i16_in_i32", 3001, 6, 4),
+    # around one look-ahead batch of the chain (1024 samples = 128 rounds: the last batch reloads itself
+    # at b = 0), with a partial second group of 16 frames
+    ("u16", 1016, 17, 0), ("u16", 1023, 17, 0), ("u16", 1024, 17, 0), ("u16", 1025, 17, 0), ("u16", 1032, 17, 0),
+    ("u16", 1033, 17, 0), ("u16", 2047, 17, 0), ("u16", 1025, 18, 6), ("i16_in_i32", 1024, 17, 0),
+    ("i16_in_i32", 1033, 3, 4)])
 def test_checksum_vs_oracle(prod, eng, orc_ext, kind, n, nf, pad):
     rng = np.random.default_rng(n * 131 + nf)
     sb = 4 if kind == "i16_in_i32" else 2

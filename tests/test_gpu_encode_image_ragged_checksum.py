@@ -1,6 +1,6 @@
 """cmp_gpu_compress_image with CMP_GPU_OPT_IMAGE_RAGGED and
 CMP_GPU_OPT_IMAGE_RAGGED_CHECKSUM: checksum-enabled contexts in ragged pieces
-(ck_ragged.hip, enc_ragged.hip).  The options change the
+(checksum.hip, enc_ragged.hip).  The options change the
 schedule only, so truth is what it is without them: the CPU oracle's call loop
 over the same table (tests/encode_image_helpers.py `truth`, which honours
 checksum_enabled).  After every call the sizes, the offsets, the image bytes,
